@@ -2,7 +2,11 @@
 """Benchmark of the approximate-count stage (errorCount, approx_counter.cpp:531-601).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|cfg5]
-                    [--scaling weak|strong]
+                    [--scaling weak|strong] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(`--dump-outputs DIR`: the counts of the last timed step as DIR/counts_start.npy
+and DIR/counts_end.npy first).  Every other leg below runs only with `--full`.
 
 A step is one pass of the stage BASELINE.md defines over one batch: both read
 ends of one run (start + end windows, approx_counter.cpp:858), each against its
@@ -25,7 +29,8 @@ ONE sample and gives rank r its contiguous shard (balanced by bases,
 approx_counter_amd/shard.py).  Either way each step ends with one RCCL
 all-reduce (sum) of the per-candidate count vector and its copy to the host.
 
-Also reported (never as `value`): `kernel_ms` / `kernel_kmer_bp_per_s`, the
+Also reported with `--full` (never as `value`): the `exact` block and the
+`cpu_baseline`; `kernel_ms` / `kernel_kmer_bp_per_s`, the
 count kernel alone on device-resident inputs (HIP events around every 5th
 launch, on the launch stream), the basis of `roofline`; `pipelined`, the same
 host-buffer steps issued back to back with ac_error_count_jobs_submit (a step's
@@ -111,7 +116,16 @@ def parse():
     ap.add_argument("--event-every", type=int, default=5,
                     help="bracket every N-th kernel-leg launch with HIP events (each event is a queue "
                          "packet of its own: ~3 us between launches when every launch is bracketed)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the kernel-only leg and its roofline, the "
+                         "pipelined leg, the exact-count block and the CPU baseline (each can still be switched off "
+                         "by its --no-... option); without it a run times the stage's steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write the counts the last timed step returned to DIR/counts_start.npy "
+                         "and DIR/counts_end.npy (float64, one count per candidate, in candidate order)")
     a = ap.parse_args()
+    if not a.full:
+        a.no_cpu_baseline = a.no_kernel_leg = a.no_pipelined = a.no_exact = True
     for key, v in CONFIGS[a.config].items():
         if getattr(a, key) is None:
             setattr(a, key, v)
@@ -534,18 +548,23 @@ def main():
                     dist.all_reduce(host)
                 h_counts.copy_(host)
 
+    # 50 ms of untimed steps bring the device to its sustained clock before the warmup (a cold GPU runs
+    # the kernel ~8 % slower for its first ~10 ms of load); with --full the legs above have done that already.
+    # (N > 1: the steps hold a collective, so their number must not depend on a rank's clock.)
+    if world == 1:
+        t_ramp = time.perf_counter()
+        while time.perf_counter() - t_ramp < 0.05:
+            step()
     for _ in range(args.warmup):
         step()
-    # the pool that packs the timed steps: made by the first stage call (its size is the plan's, or
-    # AC_HOST_THREADS when set), so read after that call, not from the plan before it
-    pool_participants, pool_cpus = host_pool_cpus()
-    if world > 1:
-        print(f"[bench] rank {rank} (local {local}): host pool {pool_participants} participants on CPUs "
-              f"{_ranges(pool_cpus)}", file=sys.stderr, flush=True)
-    torch.cuda.synchronize(dev)
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize(dev)
+    # A synchronous step returns with its counts on the host and leaves nothing in flight, so only the
+    # submit form is synchronised here: a device synchronise after the hundreds of untimed calls above
+    # made the next ~4 steps 10-30 % slower (145, 135, 133, 119 us, then 112; without it 123, 112, ...).
+    if submit_form:
+        torch.cuda.synchronize(dev)
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize(dev)
     cg0 = cgroup_cpu_stat()  # CPU-quota throttling over the timed steps
     t0 = time.perf_counter()
     marks = []
@@ -557,10 +576,29 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     cg1 = cgroup_cpu_stat()
+    # the pool that packed the timed steps: made by the first stage call (its size is the plan's, or
+    # AC_HOST_THREADS when set), so read after the steps, not from the plan before them
+    pool_participants, pool_cpus = host_pool_cpus()
+    if world > 1:
+        print(f"[bench] rank {rank} (local {local}): host pool {pool_participants} participants on CPUs "
+              f"{_ranges(pool_cpus)}", file=sys.stderr, flush=True)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: the synchronous stage's per-end uint64 counts
+        # (ac_error_count_jobs writes them into the job's arrays), or the submit form's uint32 count
+        # vector on the host (all ends concatenated; N > 1: summed over the ranks)
+        if not submit_form:
+            last = jobs.results()
+        else:
+            flat = h_counts.numpy().view(np.uint32)[: jobs.n_counts]
+            last = np.split(flat, np.cumsum(n_c)[:-1])
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for e, cnt in zip(ends, last):
+            np.save(os.path.join(args.dump_outputs, f"counts_{e}.npy"), np.asarray(cnt, dtype=np.float64))
 
     if args.verify and world == 1:  # (N > 1: tests/test_gpu_multirank.py covers the sharded path)
         import oracle

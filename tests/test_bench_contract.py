@@ -37,6 +37,36 @@ def test_cfg4_is_strong_scaling(monkeypatch):
     assert (a.k, a.sn, a.sl, a.lim, a.scaling) == (16, 1_000_000, 100, 500, "strong")
 
 
+def test_plain_run_times_the_stage_alone(monkeypatch):
+    """Without --full none of the legs beside the headline figure runs; with it each one does
+    unless its own --no-... option is given."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and not a.verify
+    assert a.no_kernel_leg and a.no_pipelined and a.no_exact and a.no_cpu_baseline
+    assert (a.steps, a.warmup) == (7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-exact", "--dump-outputs", "some/dir"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "some/dir"
+    assert a.no_exact and not (a.no_kernel_leg or a.no_pipelined or a.no_cpu_baseline)
+
+
+def test_workload_is_the_same_from_run_to_run():
+    """--dump-outputs compares two builds output for output: the same arguments give the same inputs."""
+    import argparse
+
+    import numpy as np
+
+    args = argparse.Namespace(k=16, sn=300, sl=100, lim=50, read_len=400, seed=1, scaling="weak")
+    a, units_a = bench.build_workload(args, 0, 1)
+    b, units_b = bench.build_workload(args, 0, 1)
+    assert units_a == units_b > 0
+    for e in ("start", "end"):
+        assert np.array_equal(a[e]["kmers"], b[e]["kmers"])
+        assert len(a[e]["windows"]) == len(b[e]["windows"])
+        assert all(np.array_equal(x, y) for x, y in zip(a[e]["windows"], b[e]["windows"]))
+
+
 def test_cpu_share_reports_nproc():
     n, quota = bench.cpu_share()
     assert n == len(os.sched_getaffinity(0))

@@ -10,6 +10,7 @@ EVERY candidate and window against `oracle.count_myers` (errorCount,
 approx_counter.cpp:531-601), on the very workload objects bench.py builds
 (`bench.build_workload`), so the timed path and the checked path are one."""
 import argparse
+import functools
 
 import numpy as np
 import pytest
@@ -33,6 +34,13 @@ def _expected(k, wl):
     return [oracle.count_myers(k, wl[e]["kmers"], wl[e]["windows"], THREADS) for e in ENDS]
 
 
+@functools.lru_cache(maxsize=None)
+def _cfg2():
+    """cfg2 as bench.py builds it, its units per step and the oracle's counts (computed once, shared, read-only)."""
+    wl, units = bench.build_workload(_bench_args("cfg2"), 0, 1)
+    return wl, units, _expected(16, wl)
+
+
 def _samples(wl, where):
     smp = [ac.Dna5Sample.from_windows(wl[e]["windows"]) for e in ENDS]
     return [x.pinned() for x in smp] if where == "pinned" else smp
@@ -46,12 +54,10 @@ def test_bench_cfg2_stage_bit_exact(where):
     mode = 2  # (cfg2's 20k windows are host-packed on pinned memory too: the default policy)
     import torch
 
-    args = _bench_args("cfg2")
-    wl, units = bench.build_workload(args, 0, 1)
+    wl, units, exp = _cfg2()
     assert [wl[e]["kmers"].size for e in ENDS] == [500, 500]
     assert [len(wl[e]["windows"]) for e in ENDS] == [10_000, 10_000]
     assert units == sum(500 * sum(int(w.size) for w in wl[e]["windows"]) for e in ENDS)
-    exp = _expected(16, wl)
     jobs = ac.Jobs([(wl[e]["kmers"], smp) for e, smp in zip(ENDS, _samples(wl, where))])
     with ac.ApproxCounter(0) as c:
         for i in range(6):
@@ -94,6 +100,33 @@ def test_bench_cfg4_rank_shard_submit_bit_exact(rank, where):
         sync = c.count_jobs(16, jobs)
         for g, x in zip(sync, exp):
             assert np.array_equal(g, x)
+
+
+def test_plain_bench_run_dumps_the_timed_counts(tmp_path):
+    """A plain run (no --full) times its --steps steps and nothing else, says so on the line
+    (steps, ms_per_step, none of the --full blocks) and with --dump-outputs writes the counts of
+    the last timed step, one float64 file per read end, equal to the oracle's on bench.py's own
+    workload: two builds can be compared output for output."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "dump")], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert line["metric"] == bench.METRIC and line["unit"] == "kmer*bp/s" and line["dtype"] == "u32"
+    assert line["higher_is_better"] is True
+    assert line["value"] == pytest.approx(line["config"]["kmer_bp_per_step"] / (line["ms_per_step"] * 1e-3), rel=1e-9)
+    for key in ("kernel_ms", "roofline", "pipelined", "exact", "cpu_baseline"):
+        assert key not in line, key
+    for e, x in zip(ENDS, _cfg2()[2]):
+        got = np.load(tmp_path / "dump" / f"counts_{e}.npy")
+        assert got.dtype == np.float64 and got.shape == (500,)
+        assert np.array_equal(got, x.astype(np.float64)), e
 
 
 def test_bench_line_reports_the_pool_that_ran():

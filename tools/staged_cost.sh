@@ -7,7 +7,7 @@ root=${GRAFT_REPO_ROOT:-$(pwd)}
 for m in 3 1; do
   d=$root/gpurun_out/${tag}_early$m
   ( export AC_STAGE_EARLY=$m && cd /tmp && export TMPDIR=/tmp && timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$d" -o run -- \
-      python3 "$root/bench.py" --steps 200 --warmup 10 --no-cpu-baseline --no-pipelined --kernel-launches 100 ) \
+      python3 "$root/bench.py" --full --steps 200 --warmup 10 --no-cpu-baseline --no-pipelined --kernel-launches 100 ) \
       > "$d.log" 2>&1 || { echo "AC_STAGE_EARLY=$m failed"; tail -5 "$d.log"; exit 1; }
   echo "== AC_STAGE_EARLY=$m"
   python3 "$root/tools/prof_summary.py" "$d" | grep wm2_count
