@@ -3,23 +3,44 @@
 #   approx_counter_amd/lib/libac_host.so              host stages' C ABI (tests of the CLI's CPU stages)
 #   approx_counter_amd/bin/adaptFinder                the drop-in CLI (host C++ + the C-ABI library)
 #   oracle/_build/libac_oracle.so                     CPU oracle (tests only)
-HIPCC ?= /opt/rocm/bin/hipcc
+#
+# A/B builds (tools/variants.sh, variant_dir.sh, variant_rev.sh) build the first of these only, from
+# another source tree and / or with more flags, into a directory of their own:
+#   make lib SRC=<tree holding include/ and approx_counter_amd/csrc/> OUT=<dir> EXTRA_FLAGS="-DFLAG=.."
+# puts OUT/libapprox_counter_amd.so (objects in OUT/obj).
+ROCM_PATH ?= /opt/rocm
+HIPCC ?= $(ROCM_PATH)/bin/hipcc
 ARCH ?= gfx950
-HIPFLAGS ?= -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -Wall
+EXTRA_FLAGS ?=
+SRC ?= .
+HIPFLAGS ?= -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -Wall $(EXTRA_FLAGS)
 # wm_count: keep the queue-claim atomic a plain returning atomic (the optimizer's wave-aggregated
 # form waits for the result at once, exposing the claim latency the kernel hides behind a window)
 WM_FLAGS ?= -mllvm -amdgpu-atomic-optimizer-strategy=None
 PKG := approx_counter_amd
-CSRC := $(PKG)/csrc
+INC := $(SRC)/include
+CSRC := $(SRC)/$(PKG)/csrc
 LIBDIR := $(PKG)/lib
+ifdef OUT
+LIB := $(OUT)/libapprox_counter_amd.so
+OBJDIR := $(OUT)/obj
+else
 LIB := $(LIBDIR)/libapprox_counter_amd.so
 OBJDIR := build/obj
+endif
 
-DEV_SRC := $(CSRC)/wm_count.hip $(CSRC)/exact_count.hip $(CSRC)/capi.cpp $(CSRC)/host_pack.cpp
-HDRS := include/approx_counter_amd.h include/approx_counter_amd_testing.h $(CSRC)/wm_count.h $(CSRC)/exact_count.h $(CSRC)/host_pack.h
+# the C-ABI layer: host code over the HIP runtime (hipcc as a C++ compiler: no kernel in these) ...
+CAPI := capi count_launch capi_exact capi_comm
+# ... and plain host C++ (g++): the worker pool + AVX packer, the jobs stage's plan
+HOSTONLY := host_pack stage_plan
+HDRS := $(INC)/approx_counter_amd.h $(INC)/approx_counter_amd_testing.h $(CSRC)/wm_count.h $(CSRC)/exact_count.h \
+	$(CSRC)/host_pack.h $(CSRC)/nrec.h $(CSRC)/ctx.h $(CSRC)/stage_plan.h
+INCS := -I$(INC) -I$(CSRC)
+# host-only code that includes the HIP headers (no kernel, no <<<>>>)
+HIP_HOST := -D__HIP_PLATFORM_AMD__ -I$(ROCM_PATH)/include
 
 CXX ?= g++
-HOST_CXXFLAGS ?= -O3 -std=c++17 -fPIC -Wall -Wextra
+HOST_CXXFLAGS ?= -O3 -std=c++17 -fPIC -Wall -Wextra $(EXTRA_FLAGS)
 HOSTDIR := $(CSRC)/host
 HOST_SRC := $(HOSTDIR)/host_stages.cpp
 HOST_HDRS := $(HOSTDIR)/host_stages.h include/approx_counter_host.h include/approx_counter_amd.h
@@ -29,25 +50,32 @@ CLI := $(BINDIR)/adaptFinder
 
 all: $(LIB) $(HOSTLIB) $(CLI) oracle
 
+lib: $(LIB)
+
 $(OBJDIR)/wm_count.o: $(CSRC)/wm_count.hip $(CSRC)/wm_tid_blocks.inc $(CSRC)/wm_window_loop.inc $(HDRS)
 	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) -Iinclude -I$(CSRC) -c $< -o $@
+	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) -c $< -o $@
 
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) -Iinclude -I$(CSRC) -c $< -o $@
+	$(HIPCC) $(HIPFLAGS) $(INCS) -c $< -o $@
 
-$(OBJDIR)/capi.o: $(CSRC)/capi.cpp $(HDRS)
+# the jobs stage holds a kernel (the stage's copy kernel)
+$(OBJDIR)/jobs_stage.o: $(CSRC)/jobs_stage.cpp $(HDRS)
 	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) -x hip -Iinclude -I$(CSRC) -c $< -o $@
+	$(HIPCC) $(HIPFLAGS) -x hip $(INCS) -c $< -o $@
 
-# host staging (worker pool + AVX2 packer): plain host C++, no device code
-$(OBJDIR)/host_pack.o: $(CSRC)/host_pack.cpp $(CSRC)/host_pack.h
+$(CAPI:%=$(OBJDIR)/%.o): $(OBJDIR)/%.o: $(CSRC)/%.cpp $(HDRS)
 	@mkdir -p $(OBJDIR)
-	$(CXX) $(HOST_CXXFLAGS) -c $< -o $@
+	$(HIPCC) $(filter-out --offload-arch=%,$(HIPFLAGS)) -x c++ $(HIP_HOST) $(INCS) -c $< -o $@
 
-$(LIB): $(OBJDIR)/wm_count.o $(OBJDIR)/exact_count.o $(OBJDIR)/capi.o $(OBJDIR)/host_pack.o
-	@mkdir -p $(LIBDIR)
+# (stage_plan.cpp reads the kernel's constants from wm_count.h, which includes the HIP headers)
+$(HOSTONLY:%=$(OBJDIR)/%.o): $(OBJDIR)/%.o: $(CSRC)/%.cpp $(HDRS)
+	@mkdir -p $(OBJDIR)
+	$(CXX) $(HOST_CXXFLAGS) $(HIP_HOST) $(INCS) -c $< -o $@
+
+$(LIB): $(OBJDIR)/wm_count.o $(OBJDIR)/exact_count.o $(OBJDIR)/jobs_stage.o $(CAPI:%=$(OBJDIR)/%.o) $(HOSTONLY:%=$(OBJDIR)/%.o)
+	@mkdir -p $(dir $@)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -pthread
 
 $(HOSTLIB): $(HOST_SRC) $(HOSTDIR)/host_capi.cpp $(HOST_HDRS)
@@ -64,9 +92,9 @@ oracle:
 
 asm: $(CSRC)/wm_count.hip $(CSRC)/wm_tid_blocks.inc $(CSRC)/wm_window_loop.inc $(HDRS)
 	@mkdir -p build/asm
-	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) -Iinclude -I$(CSRC) --cuda-device-only -S $< -o build/asm/wm_count.s
+	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) --cuda-device-only -S $< -o build/asm/wm_count.s
 
 clean:
 	rm -rf build $(LIBDIR) $(BINDIR) oracle/_build
 
-.PHONY: all oracle asm clean
+.PHONY: all lib oracle asm clean

@@ -85,7 +85,7 @@ struct ExactArgs {
     uint32_t* slab;    // [slab][super]: h1's column sums over EXACT_SCAN_SLAB rows (the level-1 scan)
     uint32_t* bstart;  // nb + 1
     uint32_t nb_log2;
-    uint32_t s_log2;    // super-buckets: nb_log2 - s_log2 <= 6
+    uint32_t s_log2;    // super-buckets: nb_log2 - s_log2 <= AC_SUB_LOG2 (at most EXACT_MAX_SUB buckets in each)
     uint32_t n_chunks;  // level-1 grid: ceil(key capacity / exact_part_chunk(k))
     uint32_t n_chunks2; // level-2 grid bound: n_chunks + 2^s_log2
     uint64_t key_cap;

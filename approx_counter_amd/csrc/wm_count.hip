@@ -881,7 +881,7 @@ __device__ __forceinline__ void count_body(const LaunchArgs& a, BlockLds<words_f
         if (wib == 0) {
             uint32_t r = ~0u;
             const bool equal = sg.ulen != AC_NO_ULEN && sg.n_kmers;
-            // (the copier workgroups stage every chunk: a launch with chunks has them, capi.cpp
+            // (the copier workgroups stage every chunk: a launch with chunks has them, count_launch.cpp
             // stage_copiers; round 3's wave-0 tickets in every workgroup were removed in round 5)
             if (!a.copier_wgs) {
                 if (lane == 0) atomicOr(a.err, AC_DEVERR_STAGE);

@@ -60,7 +60,7 @@ def main():
         env = dict(os.environ, AC_HOST_THREADS=str(part))
         if cpus:
             env["AC_PACK_CPUS"] = cpulist(cpus)
-        # tasks of 2,048 windows: the early launch's task size for a call this large (capi.cpp)
+        # tasks of 2,048 windows: the early launch's task size for a call this large (stage_plan.cpp)
         return subprocess.Popen([exe, str(a.n), str(a.iters), "2048", "1"], env=env, stdout=subprocess.PIPE,
                                 stderr=subprocess.STDOUT, text=True)
 
