@@ -34,7 +34,7 @@ CAPI := capi count_launch capi_exact capi_comm
 # ... and plain host C++ (g++): the worker pool + AVX packer, the jobs stage's plan
 HOSTONLY := host_pack stage_plan
 HDRS := $(INC)/approx_counter_amd.h $(INC)/approx_counter_amd_testing.h $(CSRC)/wm_count.h $(CSRC)/exact_count.h \
-	$(CSRC)/host_pack.h $(CSRC)/nrec.h $(CSRC)/ctx.h $(CSRC)/stage_plan.h
+	$(CSRC)/host_pack.h $(CSRC)/nrec.h $(CSRC)/ctx.h $(CSRC)/stage_plan.h $(CSRC)/bs_nfa.h
 INCS := -I$(INC) -I$(CSRC)
 # host-only code that includes the HIP headers (no kernel, no <<<>>>)
 HIP_HOST := -D__HIP_PLATFORM_AMD__ -I$(ROCM_PATH)/include
@@ -52,7 +52,7 @@ all: $(LIB) $(HOSTLIB) $(CLI) oracle
 
 lib: $(LIB)
 
-$(OBJDIR)/wm_count.o: $(CSRC)/wm_count.hip $(CSRC)/wm_tid_blocks.inc $(CSRC)/wm_window_loop.inc $(HDRS)
+$(OBJDIR)/wm_count.o: $(CSRC)/wm_count.hip $(CSRC)/wm_tid_blocks.inc $(CSRC)/wm_window_loop.inc $(CSRC)/bs_count.inc $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) -c $< -o $@
 
@@ -90,7 +90,7 @@ $(CLI): $(HOSTDIR)/adaptfinder.cpp $(HOST_SRC) $(HOST_HDRS) $(LIB)
 oracle:
 	$(MAKE) -s -C oracle
 
-asm: $(CSRC)/wm_count.hip $(CSRC)/wm_tid_blocks.inc $(CSRC)/wm_window_loop.inc $(HDRS)
+asm: $(CSRC)/wm_count.hip $(CSRC)/wm_tid_blocks.inc $(CSRC)/wm_window_loop.inc $(CSRC)/bs_count.inc $(HDRS)
 	@mkdir -p build/asm
 	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) --cuda-device-only -S $< -o build/asm/wm_count.s
 

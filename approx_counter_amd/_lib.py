@@ -131,6 +131,9 @@ def load():
     if hasattr(L, "ac_testing_stage_hooks"):  # (an A/B build of an older ABI may lack it)
         L.ac_testing_stage_hooks.argtypes = [ctypes.c_uint32]
         L.ac_testing_stage_hooks.restype = ctypes.c_uint32
+    if hasattr(L, "ac_testing_last_count_kernel"):  # (an A/B build of an older library lacks it)
+        L.ac_testing_last_count_kernel.argtypes = [vp]
+        L.ac_testing_last_count_kernel.restype = ctypes.c_int
     if hasattr(L, "ac_host_alloc"):  # (ABI >= 7; A/B builds of older ABIs lack it)
         L.ac_host_alloc.argtypes = [ctypes.c_size_t, ctypes.POINTER(vp)]
         L.ac_host_alloc.restype = ctypes.c_int

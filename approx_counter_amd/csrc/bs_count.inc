@@ -1,0 +1,514 @@
+// bs_count.inc -- the bit-sliced count kernel (DESIGN.md §4e), included by wm_count.hip inside its
+// anonymous namespace: it shares that file's staging protocol (stage_copy, stage_copy_dp, stage_gate),
+// work queues' layout and count hand-off, and differs in how a wave maps onto the work.
+//
+// Mapping: bit j of a lane word is candidate j of a block of 32 (bs_nfa.h); a candidate group
+// (BS_GROUP candidates, the host's cands_per_wave, so the launch plan, the acc slots and the groups'
+// error words are those of the word-parallel kernel) takes LW = max(2, next_pow2(ceil(candidates / 32)))
+// lanes per window (bs_lane_shift), lane % LW = the candidate block, and a wave counts a ROW of 64 / LW
+// consecutive windows at once.  A work item is `chunk` rows.
+// Text is per lane: every lane loads its window's slot itself (buffer loads at its own offset, the
+// next row's while this one is counted) and the window's first lane parks it in LDS -- 24 words per
+// window, 16 of codes and 8 of N bits -- from where one code word is read back per 16 bases; per
+// base the lane forms its character (2-bit code + 4 x N bit) and reads nE[0..K-1] for it from the
+// workgroup's ~Eq table in LDS with K / 4 ds_read_b128.
+// Table layout: [character 0..7][quad 0..K/4-1][block 0..BS_LWMAX-1] x 16 B, the characters BS_ROW
+// bytes further apart than their quads need, so that characters of different parity start in
+// different bank halves (windows of one ds_read_b128 lane group that hold the same character read
+// one address).  Characters 4..7 (an N base, whatever its code bits) are all ones, as are the bits
+// of candidate slots past n_kmers.
+// Only equal-window launches (every live segment has ulen in 1..256) with K in AC_BS_K_LIST.
+constexpr uint32_t BS_GROUP = 64u * 2u * (uint32_t)words_for(2, false);  // = cands_per_wave(2, *)
+static_assert(words_for(2, false) == words_for(2, true), "one group size for plain and staged launches");
+constexpr uint32_t BS_LWMAX = BS_GROUP / 32u;       // lanes per window of a full group
+constexpr uint32_t BS_ROW = BS_LWMAX * 16u;         // bytes of one (character, quad) table row
+
+template <int K>
+struct BsLds {
+    static constexpr uint32_t QUADS = K / 4;
+    static constexpr uint32_t CHAR_STRIDE = (QUADS + 1u) * BS_ROW;
+    alignas(16) uint32_t tab[8u * CHAR_STRIDE / 4u];  // characters 4..7: an N base, whatever its code bits
+    uint32_t cnt[BS_GROUP];
+    uint32_t stage_r;
+    // per wave, two buffers of a row's text: up to 32 windows' slots of up to 16 code words, and the
+    // 8 words of N bits that go with them
+    alignas(16) uint32_t text[AC_WAVES_PER_BLOCK][2][32][24];
+};
+
+typedef uint32_t bs_v4u __attribute__((ext_vector_type(4)));
+
+// nE[0..K-1] of this lane's block for the character whose table row starts at byte `addr`
+// (character * CHAR_STRIDE + block * 16): K / 4 ds_read_b128 at immediate offsets.
+template <int K>
+__device__ __forceinline__ void bs_read(const BsLds<K>& lds, uint32_t addr, uint32_t (&e)[K]) {
+    const char* p = (const char*)lds.tab + addr;
+#pragma unroll
+    for (int q = 0; q < K / 4; ++q) {
+        const bs_v4u v = *(const bs_v4u*)(p + q * BS_ROW);
+        e[4 * q] = v.x;
+        e[4 * q + 1] = v.y;
+        e[4 * q + 2] = v.z;
+        e[4 * q + 3] = v.w;
+    }
+}
+
+// The table row of base b of a word of 2-bit codes and its N bits: character = code + 4 x N bit.
+template <int K>
+__device__ __forceinline__ uint32_t bs_row(uint32_t code, uint32_t nm, uint32_t b, uint32_t lane_off) {
+    const uint32_t c = ((nm >> b & 1u) << 2) | ((code >> (2u * b)) & 3u);
+    return c * BsLds<K>::CHAR_STRIDE + lane_off;
+}
+
+// 4 bases of every lane's window -- the one copy of the NFA code in the kernel (with a second, e.g. a
+// 16-base form beside a tail form, the register allocator spilled the NFA state around both):
+// `code` / `nm` hold their 2-bit codes and N bits from bit 0, `ncode` / `nnm` the next block's, `ea`
+// comes in with the first base's table rows and leaves with the next block's first base's, so every
+// base's table reads are issued one base ahead.  Bases in pairs: 1.5 ops of hit accumulation per base.
+// One form for windows with and without N: a row of windows has an N in most blocks once some of
+// its windows do.
+template <int K>
+__device__ __forceinline__ void bs_block4(bs::State<K>& s, const BsLds<K>& lds, uint32_t code, uint32_t nm, uint32_t ncode,
+                                          uint32_t nnm, uint32_t lane_off, uint32_t (&ea)[K]) {
+    uint32_t eb[K];
+#pragma unroll
+    for (uint32_t b = 0; b < 4u; b += 2u) {
+        bs_read<K>(lds, bs_row<K>(code, nm, b + 1u, lane_off), eb);
+        bs::advance<K>(s, ea);
+        const bs::Last x = bs::last<K>(s);
+        bs_read<K>(lds, b + 2u < 4u ? bs_row<K>(code, nm, b + 2u, lane_off) : bs_row<K>(ncode, nnm, 0u, lane_off), ea);
+        bs::advance<K>(s, eb);
+        bs::hits2<K>(s, x);
+    }
+}
+
+template <int K, bool STAGED>
+__device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
+    static_assert(K % 4 == 0 && K <= 32, "the table is read in quads of positions; a k-mer is one 64-bit word");
+    constexpr uint32_t CS = BsLds<K>::CHAR_STRIDE;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t wave = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wib;
+    stamp(wave, 0);
+    // The deal of workgroups to block-queues, the sub-queues and the staging wait are count_body's.
+    const uint32_t nqb = a.n_queues / WAVES_PER_BLOCK;
+    const uint32_t blocks = (uint32_t)(a.total_waves / WAVES_PER_BLOCK);
+    const uint32_t rank = blockIdx.x / nqb;
+    auto shift = [&](uint32_t r) { return (r + (r >> 3) * 4u) % nqb; };
+    const uint32_t bq = (blockIdx.x % nqb + shift(rank)) % nqb;
+    auto wgs_of = [&](uint32_t qb) {
+        return blocks / nqb + ((qb + nqb - shift(blocks / nqb)) % nqb < blocks % nqb ? 1u : 0u);
+    };
+    const uint32_t q = bq * WAVES_PER_BLOCK + wib;
+    int si = 0;
+#pragma unroll
+    for (int i = 1; i < AC_MAX_SEGS; ++i)
+        if (i < (int)a.n_segs && q >= a.seg[i].queue_begin) si = i;
+    const SegDev& sg = a.seg[si];
+    const uint32_t ql = q - sg.queue_begin;
+    const uint32_t g = ql / sg.subq, j = ql % sg.subq;
+
+    uint32_t has_n = sg.has_n;
+    bool skip = false;
+    bool partial = false;  // staged: the segment is not known complete; rows go through the gate
+    uint32_t v_lo = 0, v_hi = 0;
+    uint32_t* st_words = nullptr;
+    if (STAGED && sg.stage_chunks) {
+        st_words = a.stage + AC_STAGE_L_SEG(si) * AC_QUEUE_LINE;
+        const uint32_t pre_bytes = sg.stage_codes_off;
+        if (blockIdx.x < a.copier_wgs) {  // copier workgroup: every wave serves every segment's tickets
+            for (uint32_t i2 = 0; i2 < a.n_segs; ++i2) {
+                const uint32_t s2 = (blockIdx.x + i2) % a.n_segs;
+                const SegDev& c2 = a.seg[s2];
+                if (!c2.stage_chunks) continue;
+#ifndef AC_NO_DEVICE_PACK
+                const bool ok = c2.dp_src
+                                    ? stage_copy_dp(c2, a.stage + AC_STAGE_L_SEG(s2) * AC_QUEUE_LINE, a.gen, a.err)
+                                    : stage_copy(c2.stage_src, c2.stage_dst, c2.stage_chunks,
+                                                 c2.stage_codes_off / AC_STAGE_CHUNK, a.host_hdr + s2 * AC_QUEUE_LINE,
+                                                 a.stage + AC_STAGE_L_SEG(s2) * AC_QUEUE_LINE, c2.stage_gen, a.gen, s2);
+#else
+                const bool ok = stage_copy(c2.stage_src, c2.stage_dst, c2.stage_chunks, c2.stage_codes_off / AC_STAGE_CHUNK,
+                                           a.host_hdr + s2 * AC_QUEUE_LINE, a.stage + AC_STAGE_L_SEG(s2) * AC_QUEUE_LINE,
+                                           c2.stage_gen, a.gen, s2);
+#endif
+                if (!__builtin_amdgcn_readfirstlane((uint32_t)ok))
+                    if (lane == 0) atomicOr(a.err, AC_DEVERR_STAGE);
+            }
+        }
+        if (wib == 0) {
+            uint32_t r = ~0u;
+            if (!a.copier_wgs) {
+                if (lane == 0) atomicOr(a.err, AC_DEVERR_STAGE);
+            } else {  // only the k-mers (the ~Eq table) are needed before counting starts
+                r = (uint32_t)stage_gate(st_words, sg.stage_gen, sg.stage_chunks, blockIdx.x % AC_STAGE_REPL, a.gen, 0u,
+                                         8u * sg.n_kmers, a.err, pre_bytes);
+            }
+            if (lane == 0) lds.stage_r = r;
+            stamp(wave, 7);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        const uint32_t r = __builtin_amdgcn_readfirstlane(lds.stage_r);
+        skip = r == ~0u;
+        partial = r == 2u;
+        has_n = (skip || partial) ? 0u : r;
+    }
+    const uint32_t* codes_p = sg.codes;
+    const uint32_t* nmask_p = sg.nmask;
+    uint32_t code_bytes = (uint32_t)(sg.n_bases >> 2);
+    uint32_t nmask_bytes = (uint32_t)(sg.n_bases >> 3);
+    asm volatile("" : "+s"(codes_p), "+s"(nmask_p), "+s"(code_bytes), "+s"(nmask_bytes));
+    const __amdgpu_buffer_rsrc_t r_codes = __builtin_amdgcn_make_buffer_rsrc((void*)codes_p, 0, (int)code_bytes, 0x00020000);
+    // (the N bitmap is read only by windows that need it, and -- staged -- only once the segment is complete)
+    const __amdgpu_buffer_rsrc_t r_nmask = __builtin_amdgcn_make_buffer_rsrc((void*)nmask_p, 0, (int)nmask_bytes, 0x00020000);
+    uint32_t* g_queue = a.queue + ((uint64_t)a.bank * a.qstride + sg.queue_begin + g * sg.subq) * AC_QUEUE_LINE;
+    uint32_t ulen = sg.ulen;
+    asm volatile("" : "+s"(ulen));
+    const uint32_t sbytes = ((ulen + 31u) & ~31u) >> 2;  // bytes of a window's slot of code words (8..64)
+    uint32_t seg_nw = sg.n_windows, seg_chunk = sg.chunk, seg_qb = sg.queue_begin;
+    asm volatile("" : "+s"(seg_nw), "+s"(seg_chunk), "+s"(seg_qb));
+    uint32_t st_codes_off = STAGED ? sg.stage_codes_off : 0u, st_nchunks = STAGED ? sg.stage_chunks : 0u;
+    uint32_t* st_gen = STAGED ? sg.stage_gen : nullptr;
+    if constexpr (STAGED) asm volatile("" : "+s"(st_codes_off), "+s"(st_nchunks), "+s"(st_gen));
+    const bool rec = sg.nrec != 0u;  // inline N records (nrec.h) in the top bits of every slot's last code word
+    const uint32_t rec_pb = nrec_pos_bits(ulen);
+
+    // The group's lanes per window, and this lane's place in a row.
+    const uint32_t ng = min(BS_GROUP, sg.n_kmers - g * BS_GROUP);
+    const uint32_t lwsh = bs_lane_shift(ng), LW = 1u << lwsh, wpr = 64u >> lwsh;
+    const uint32_t wl = lane >> lwsh, blk = lane & (LW - 1u);
+    const uint32_t lane_off = blk * 16u;
+    const uint32_t n_rows = (seg_nw + wpr - 1u) >> (6u - lwsh);
+
+    // Counters of the other queue bank are zeroed for the next launch.
+    for (uint64_t z = wave; z < a.zero_count; z += a.total_waves)
+        if (lane == 0)
+            __hip_atomic_exchange(&a.queue[((a.bank ^ 1u) * (uint64_t)a.qstride + z) * AC_QUEUE_LINE], 0u,
+                                  __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+
+    // Dynamic work queues (count_body): items of `chunk` rows, strided over the group's sub-queues; a
+    // wave's first item is static, further ones are claimed one row ahead, then stolen from siblings.
+    const uint32_t S = sg.subq;
+    const uint32_t chunk = seg_chunk;
+    const uint32_t n_items = (n_rows + chunk - 1u) / chunk;
+    uint32_t jc = j;
+    auto counter = [&](uint32_t jj) { return g_queue + (uint64_t)jj * AC_QUEUE_LINE; };
+    auto waves_in = [&](uint32_t jj) {
+        const uint32_t qq = seg_qb + g * S + jj;
+        return wgs_of(qq / WAVES_PER_BLOCK);
+    };
+    auto n_in = [&](uint32_t jj) { return jj < n_items ? (n_items - jj + S - 1u) / S : 0u; };
+    uint32_t jc_waves = waves_in(jc), jc_items = n_in(jc);
+    auto item_of = [&](uint32_t c) { return c < jc_items ? jc + c * S : n_items; };
+    auto dequeue_issue = [&]() -> uint32_t {
+        uint32_t v = 0;
+        if (lane == 0) v = __hip_atomic_fetch_add(counter(jc), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return v;
+    };
+    auto steal = [&]() -> uint32_t {
+        for (;;) {
+            uint32_t found = S;
+            for (uint32_t b = 1; b < S && found == S; b += 63u) {
+                bool have = false;
+                if (lane < 63u && b + lane < S) {
+                    const uint32_t jj = (j + b + lane) % S;
+                    const uint32_t v = __hip_atomic_load(counter(jj), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    have = waves_in(jj) + v < n_in(jj);
+                }
+                const uint64_t mk = __ballot(have);
+                if (mk) found = b + (uint32_t)__builtin_ctzll(mk);
+            }
+            if (found == S) return n_items;
+            const uint32_t jj = (j + found) % S;
+            jc = jj;
+            jc_waves = waves_in(jj);
+            jc_items = n_in(jj);
+            const uint32_t c = jc_waves + __builtin_amdgcn_readfirstlane(dequeue_issue());
+            if (c < jc_items) return item_of(c);
+        }
+    };
+
+    // Staged: the segment is complete (verdict r: 0 / 1) or skipped (~0u).
+    auto completed = [&](uint32_t r) __attribute__((always_inline)) {
+        partial = false;
+        if (r == ~0u) return false;
+        has_n = r;
+        return true;
+    };
+    // Staged early counting: before a row's fetch, every byte the fetch reads -- the row's slots, which
+    // are contiguous in the image, and the 32 bytes a lane's 16-byte loads may reach past its slot -- is
+    // in device memory and inside the N-free prefix; false = skip the segment.
+    auto gate = [&](uint32_t rr) __attribute__((always_inline)) {
+        if constexpr (STAGED) {
+            if (!partial) return true;
+            const uint32_t b0 = rr * wpr * sbytes;
+            const uint32_t r0 = st_codes_off + b0, r1 = st_codes_off + min(b0 + wpr * sbytes + 32u, code_bytes);
+            if (r0 >= v_lo && r1 <= v_hi) return true;
+            const uint64_t gr = stage_gate(st_words, st_gen, st_nchunks, blockIdx.x % AC_STAGE_REPL, a.gen, r0, r1, a.err);
+            const uint32_t r = __builtin_amdgcn_readfirstlane((uint32_t)gr);
+            if (r == 2u) {
+                v_lo = (r0 / AC_STAGE_CHUNK) * AC_STAGE_CHUNK;
+                v_hi = __builtin_amdgcn_readfirstlane((uint32_t)(gr >> 32));
+                return true;
+            }
+            return completed(r);
+        } else {
+            (void)rr;
+            return true;
+        }
+    };
+
+    // A row's text goes through LDS, so that no window's code words sit in registers while it is counted:
+    // every lane loads its window's slot (up to 64 bytes; the lanes of a window load the same lines), the
+    // window's first lane stores it into the wave's text buffer, and every chunk of 16 bases reads its
+    // one code word from there.  Two buffers: the next row's text is fetched while this row is counted.
+    // A lane without a window (a partial last row) loads from an offset past any image's range check,
+    // i.e. zeros without a memory access.
+    constexpr uint32_t NO_WINDOW = 0xffffff00u;
+    auto slot_off = [&](uint32_t rr) __attribute__((always_inline)) {
+        const uint32_t w = rr * wpr + wl;
+        return w < seg_nw ? w * sbytes : NO_WINDOW;
+    };
+    uint32_t buf = 0;   // the text buffer of the current row
+    uint32_t bufn = 0;  // bit b: buffer b's N words came with its text (a segment without records that has a bitmap)
+    auto fetch_row = [&](uint32_t rr, uint32_t bf) __attribute__((always_inline)) {
+        const uint32_t off = slot_off(rr);
+        bs_v4u* dst = (bs_v4u*)&lds.text[wib][bf][wl][0];
+        const bs_v4u t0 = __builtin_amdgcn_raw_buffer_load_b128(r_codes, off, 0, 0);
+        const bs_v4u t1 = __builtin_amdgcn_raw_buffer_load_b128(r_codes, off + 16u, 0, 0);
+        if (sbytes > 32u) {
+            const bs_v4u t2 = __builtin_amdgcn_raw_buffer_load_b128(r_codes, off + 32u, 0, 0);
+            const bs_v4u t3 = __builtin_amdgcn_raw_buffer_load_b128(r_codes, off + 48u, 0, 0);
+            if (blk == 0u) dst[2] = t2, dst[3] = t3;
+        }
+        if (blk == 0u) dst[0] = t0, dst[1] = t1;
+        const bool with_n = !rec && has_n;  // no records: every window's N bits are its bitmap words
+        if (with_n) {
+            const uint32_t noff = off == NO_WINDOW ? NO_WINDOW : off >> 1;
+            const bs_v4u n0 = __builtin_amdgcn_raw_buffer_load_b128(r_nmask, noff, 0, 0);
+            bs_v4u n1 = {0u, 0u, 0u, 0u};
+            if (sbytes > 32u) n1 = __builtin_amdgcn_raw_buffer_load_b128(r_nmask, noff + 16u, 0, 0);
+            if (blk == 0u) dst[4] = n0, dst[5] = n1;
+        }
+        bufn = (bufn & ~(1u << bf)) | ((with_n ? 1u : 0u) << bf);
+        // (the other lanes of the window read what its first lane wrote: LDS serves a wave's
+        // instructions in order; the fence keeps the compiler from moving the reads up)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    };
+
+    uint32_t item = (j < n_items && !skip) ? item_of(rank) : n_items;
+    uint32_t row = item * chunk, item_end = min(n_rows, row + chunk);
+
+    // The workgroup's ~Eq table: wave v takes candidates 64 v .. 64 v + 63 of the group (blocks 2 v and
+    // 2 v + 1), one ballot per (position, character); lane 4 i + c keeps the ballot of position i and
+    // character c and stores its two halves.  Wave 0 also writes the N rows and zeroes the counts.
+    if (!skip && (wib == 0 || 2u * wib < LW)) {
+        const uint32_t c = g * BS_GROUP + wib * 64u + lane;
+        const bool have = wib * 64u + lane < ng;
+        const uint64_t km = have ? sg.kmers[c] : 0ull;
+        uint64_t mine = ~0ull;
+#pragma unroll
+        for (uint32_t i = 0; i < (uint32_t)K; ++i) {
+            const uint32_t ch = (uint32_t)(km >> (2u * ((uint32_t)K - 1u - i))) & 3u;
+#pragma unroll
+            for (uint32_t cc = 0; cc < 4u; ++cc) {
+                const uint64_t bal = __ballot(!have || ch != cc);
+                if (lane == 4u * i + cc) mine = bal;
+            }
+        }
+        static_assert(4 * K <= 64, "one lane per (position, character)");
+        if (lane < 4u * (uint32_t)K) {
+            const uint32_t i = lane >> 2, cc = lane & 3u;
+            uint32_t* p = lds.tab + (cc * CS + (i >> 2) * BS_ROW + (i & 3u) * 4u) / 4u;
+            p[(2u * wib) * 4u] = (uint32_t)mine;
+            if (2u * wib + 1u < BS_LWMAX) p[(2u * wib + 1u) * 4u] = (uint32_t)(mine >> 32);
+        }
+    }
+    if (wib == 0) {
+        for (uint32_t x = lane; x < 4u * CS / 4u; x += 64u) lds.tab[4u * CS / 4u + x] = ~0u;
+        for (uint32_t x = lane; x < BS_GROUP; x += 64u) lds.cnt[x] = 0u;
+    }
+    bool stage_ok = true;
+    if (item < n_items) {  // (before the table barrier only the plain kernel: a staged wave waiting for
+                           // its first row must not hold its workgroup's other waves there)
+        if (!STAGED) fetch_row(row, buf);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    stamp(wave, 1);
+    if (STAGED && item < n_items) {
+        stage_ok = gate(row);
+        if (stage_ok) fetch_row(row, buf);
+        else item = n_items;
+    }
+
+    bs::VCount vc;
+    bs::vc_clear(vc);
+    // The planes' counts into the workgroup's count array (the lanes of a wave that share a candidate
+    // block, and the workgroup's waves, sum there).
+    auto flush = [&]() __attribute__((always_inline)) {
+#pragma unroll 4
+        for (uint32_t b = 0; b < 32u; ++b) {
+            const uint32_t v = bs::vc_get(vc, b);
+            if (v) __hip_atomic_fetch_add(&lds.cnt[blk * 32u + b], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        bs::vc_clear(vc);
+    };
+
+    const uint32_t nq = (ulen + 3u) >> 2;  // blocks of 4 bases per window
+    while (item < n_items) {
+        const uint32_t* text = &lds.text[wib][buf][wl][0];
+        const uint32_t my_off = slot_off(row);
+        bool has = my_off != NO_WINDOW;
+        const bool last = row + 1u >= item_end;  // the item's last row: claim the next item
+        uint32_t pending = 0;
+        uint32_t nitem = item, nrow = row + 1u;
+
+        // The window's N bits, 16 per chunk, are read from the row's buffer: they came with the text
+        // (no records), or are written here from the window's record (the top bits of its slot's last
+        // code word) -- from its N-bitmap words when the record overflowed (staged: only once the whole
+        // segment is in).  Most rows have no N at all and skip this.
+        bool row_n = (bufn >> buf & 1u) != 0u;
+        const uint32_t rc = rec ? text[(sbytes >> 2) - 1u] >> 29 : 0u;
+        if (__builtin_expect(__ballot(rc != 0u) != 0ull, 0)) {
+            const uint32_t rw = text[(sbytes >> 2) - 1u];
+            const bool ovf = has && rc == NREC_OVERFLOW;
+            if (STAGED && partial && __ballot(ovf)) {
+                const uint64_t gr = stage_gate(st_words, st_gen, st_nchunks, blockIdx.x % AC_STAGE_REPL, a.gen, 0u, ~0u, a.err);
+                if (!completed(__builtin_amdgcn_readfirstlane((uint32_t)gr))) stage_ok = false;
+            }
+            if (ovf && !has_n) {  // no bitmap for an overflowed record: skipped, reported
+                if (stage_ok) atomicOr(a.err, AC_DEVERR_WINDOW);
+                has = false;
+            }
+            uint32_t n[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+            for (uint32_t i = 0; i < 4u; ++i)
+                if (rc != NREC_OVERFLOW && i < rc) {
+                    const uint32_t pos = (rw >> nrec_pos_shift(rec_pb, i)) & ((1u << rec_pb) - 1u);
+#pragma unroll
+                    for (uint32_t x = 0; x < 8u; ++x)
+                        if ((pos >> 5) == x) n[x] |= 1u << (pos & 31u);
+                }
+            const bool use_bm = ovf && has;
+            if (__ballot(use_bm)) {
+                const uint32_t noff = use_bm ? my_off >> 1 : NO_WINDOW;
+                const bs_v4u b0 = __builtin_amdgcn_raw_buffer_load_b128(r_nmask, noff, 0, 0);
+                bs_v4u b1 = {0u, 0u, 0u, 0u};
+                if (sbytes > 32u) b1 = __builtin_amdgcn_raw_buffer_load_b128(r_nmask, noff + 16u, 0, 0);
+                if (use_bm) n[0] = b0.x, n[1] = b0.y, n[2] = b0.z, n[3] = b0.w, n[4] = b1.x, n[5] = b1.y, n[6] = b1.z, n[7] = b1.w;
+            }
+            if (blk == 0u) {
+                bs_v4u* dst = (bs_v4u*)&lds.text[wib][buf][wl][16];
+                dst[0] = bs_v4u{n[0], n[1], n[2], n[3]};
+                dst[1] = bs_v4u{n[4], n[5], n[6], n[7]};
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            row_n = true;
+        }
+        uint32_t live = has ? ~0u : 0u;  // (a lane without a window adds nothing to the counts)
+        asm volatile("" : "+v"(live));
+
+        // The window's bases in blocks of 4, the last one filled up with N: an N matches nothing, and an
+        // occurrence that would end on a filling N also ends on the window's last base at no more edits
+        // (its N bases deleted), so the filling adds no hit.  word(gc): the codes and N bits of bases
+        // 16 gc .. 16 gc + 15.
+        auto n_word = [&](uint32_t gc) __attribute__((always_inline)) {
+            const uint32_t real = ulen > 16u * gc ? min(16u, ulen - 16u * gc) : 0u;
+            const uint32_t nmw = row_n ? text[16u + (gc >> 1)] >> ((gc & 1u) * 16u) : 0u;
+            return (nmw | (0xffffu << real)) & 0xffffu;
+        };
+        bs::State<K> s;
+        bs::init<K>(s);
+        uint32_t code = text[0], nm = n_word(0u);
+        uint32_t ea[K];
+        bs_read<K>(lds, bs_row<K>(code, nm, 0u, lane_off), ea);
+        // The claim of the next item goes out 20 bases before the row's end and is read before its last
+        // block, with the next row's gate and text: late, so that the items left when the waves' first
+        // ones end go to the waves that end first, wherever they run (claimed at the row's start, a
+        // nearly one-round launch's second items all went to the first workgroups dispatched -- a few
+        // CUs ran two rounds while the others idled).
+        const uint32_t q_claim = nq > 5u ? nq - 5u : 0u, q_next = nq - 1u;
+        for (uint32_t q = 0; q < nq && stage_ok; ++q) {
+            if (__builtin_expect(q == q_claim && last, 0)) pending = dequeue_issue();
+            if (__builtin_expect(q == q_next, 0)) {  // (unlikely: the register allocator keeps the NFA state in registers around the blocks, not around this)
+                if (last) {
+                    nitem = __builtin_amdgcn_readfirstlane(item_of(jc_waves + __builtin_amdgcn_readfirstlane(pending)));
+                    if (nitem >= n_items && S > 1) nitem = __builtin_amdgcn_readfirstlane(steal());
+                    nrow = nitem * chunk;
+                }
+                if (nitem < n_items) {
+                    if (gate(nrow)) fetch_row(nrow, buf ^ 1u);
+                    else stage_ok = false;
+                }
+                // (read again, so that the rows read ahead are not kept in registers across this)
+                bs_read<K>(lds, bs_row<K>(code, nm, 0u, lane_off), ea);
+            }
+            uint32_t ncode = code >> 8, nnm = nm >> 4;
+            if ((q & 3u) == 3u) {
+                ncode = text[(q >> 2) + 1u];
+                nnm = n_word((q >> 2) + 1u);
+            }
+            bs_block4<K>(s, lds, code, nm, ncode, nnm, lane_off, ea);
+            code = ncode;
+            nm = nnm;
+        }
+        if (STAGED && !stage_ok) {  // the segment is skipped (the error word says so)
+            item = n_items;
+            break;
+        }
+        bs::vc_add(vc, s.a0, s.a1, s.a2, live);
+        if (bs::vc_full(vc)) flush();
+        if (last) item_end = min(n_rows, nrow + chunk);
+        item = nitem;
+        row = nrow;
+        buf ^= 1u;
+    }
+    if (vc.n) flush();
+    stamp(wave, 2);
+
+    // The count hand-off (count_body): one wave adds (1 << 32) + the workgroup's sum into the group's acc
+    // slots; a slot's last workgroup moves the total to the counts.
+    constexpr int Q = (int)(BS_GROUP / 64u);
+    if (STAGED) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (wib == 0) {
+        uint64_t* acc = a.acc + sg.acc_begin + g * BS_GROUP;
+        const uint32_t qb0 = (sg.queue_begin + g * sg.subq) / WAVES_PER_BLOCK, nq = sg.subq / WAVES_PER_BLOCK;
+        uint32_t n_wg = 0;
+        for (uint32_t i = 0; i < nq; ++i) n_wg += wgs_of(qb0 + i);
+        uint32_t mine[Q];
+        uint64_t old[Q];
+#pragma unroll
+        for (int qq = 0; qq < Q; ++qq) {
+            mine[qq] = lds.cnt[qq * 64 + lane];
+            old[qq] = __hip_atomic_fetch_add(&acc[qq * 64 + lane], (1ull << 32) | mine[qq], __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_AGENT);
+        }
+#pragma unroll
+        for (int qq = 0; qq < Q; ++qq) {
+            if ((uint32_t)(old[qq] >> 32) != n_wg - 1u) continue;  // not the slot's last workgroup
+            const uint32_t v = (uint32_t)old[qq] + mine[qq];
+            const uint32_t cand = g * BS_GROUP + (uint32_t)qq * 64u + lane;
+            __hip_atomic_store(&acc[qq * 64 + lane], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (cand < sg.n_kmers) {
+                if (a.add_counts) {
+                    if (v) atomicAdd(&sg.counts[cand], v);
+                } else if (STAGED && a.tag) {
+                    __hip_atomic_store((uint64_t*)sg.counts + cand, ((uint64_t)a.gen << 32) | v, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_SYSTEM);
+                } else {
+                    sg.counts[cand] = v;
+                }
+            }
+            if (STAGED && qq == 0 && lane == 0) {  // the group's error snapshot (count_body)
+                const uint32_t e = __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (a.tag)
+                    __hip_atomic_store(a.grp_err + sg.group_begin + g, ((uint64_t)a.gen << 32) | e, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_SYSTEM);
+                else if (e && a.err_out)
+                    atomicOr(a.err_out, e);
+            }
+        }
+    }
+    stamp(wave, 3);
+}

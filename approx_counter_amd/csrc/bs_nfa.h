@@ -1,0 +1,176 @@
+// bs_nfa.h -- the bit-sliced ("candidate per bit") form of the count kernel's NFA, and the
+// bit-plane counters its hits are summed in.  Plain C++ that compiles for the
+// device (bs_count.inc) and for the host (tools/bs_nfa_check.cpp, tests/test_bs_nfa.py), so the
+// code the kernel runs is the code the CPU test checks against the oracle.
+//
+// The recurrence is wm_count.hip's (Wu-Manber, complemented, free start in the text), transposed:
+// bit j of a word is candidate j of a block of 32, register i is pattern position i.  The shift
+// (D >> P)[i] = D[i-1] is then a register rename, and only position K-1 is accumulated for hits.
+// With nE[i] = the 32 candidates' ~Eq at position i under the current text character:
+//   D0'[0] = nE[0]                       D0'[i] = D0[i-1] | nE[i]
+//   Dd'[i] = (Dd[i-1] | nE[i]) & Dd-1[i] & Dd-1[i-1] & Dd-1'[i-1]          d = 1, 2
+// The zero fill of the shift makes D1[0], D2[0] and D2[1] zero for good (from the initial rows:
+// R1 has position 0 set, R2 positions 0 and 1), so they are constants here: no register, no op.
+// Per text base: K-1 ORs, 2(K-1) + 2(K-2) three-input ops, and 1.5 ops of hit accumulation when
+// bases go in pairs (step2) -- 74.5 for K = 16, for 32 candidates.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define AC_BS_FN __host__ __device__ __forceinline__
+#else
+#define AC_BS_FN inline
+#endif
+
+namespace acamd {
+namespace bs {
+
+// The instantiated pattern lengths, in one place (count_launch.cpp routes by it, bs_count.inc
+// instantiates by it).
+#define AC_BS_K_LIST(X) X(16)
+constexpr bool has_k(uint32_t k) {
+#define AC_BS_K_EQ(KK) || k == KK
+    return false AC_BS_K_LIST(AC_BS_K_EQ);
+#undef AC_BS_K_EQ
+}
+
+// v_bitop3_b32 by its truth table: bit (a << 2 | b << 1 | c) of TT is the result for inputs a, b, c.
+template <uint32_t TT>
+AC_BS_FN uint32_t bitop3(uint32_t a, uint32_t b, uint32_t c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_bitop3_b32(a, b, c, TT);
+#else
+    uint32_t r = 0;
+    for (uint32_t i = 0; i < 8; ++i)
+        if (TT >> i & 1u) r |= ((i & 4u) ? a : ~a) & ((i & 2u) ? b : ~b) & ((i & 1u) ? c : ~c);
+    return r;
+#endif
+}
+constexpr uint32_t TT_OR_AND = 0xa8;  // (a | b) & c
+constexpr uint32_t TT_AND3 = 0x80;    // a & b & c
+constexpr uint32_t TT_XOR3 = 0x96;    // a ^ b ^ c
+constexpr uint32_t TT_MAJ = 0xe8;     // majority(a, b, c)
+
+// The three rows of 32 candidates' NFAs and the AND of their last position over a window.
+template <int K>
+struct State {
+    uint32_t d0[K], d1[K], d2[K];  // d1[0], d2[0], d2[1] stay 0
+    uint32_t a0, a1, a2;           // bit clear: that level has hit somewhere in the window
+};
+
+template <int K>
+AC_BS_FN void init(State<K>& s) {
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        s.d0[i] = ~0u;
+        s.d1[i] = i >= 1 ? ~0u : 0u;
+        s.d2[i] = i >= 2 ? ~0u : 0u;
+    }
+    s.a0 = s.a1 = s.a2 = ~0u;
+}
+
+// One text base (no hit accumulation).
+template <int K>
+AC_BS_FN void advance(State<K>& s, const uint32_t (&nE)[K]) {
+    static_assert(K >= 3, "pattern length");
+    uint32_t n0[K], n1[K], n2[K];
+    n0[0] = nE[0];
+    n1[0] = 0u;
+    n2[0] = 0u;
+    n2[1] = 0u;
+#pragma unroll
+    for (int i = 1; i < K; ++i) n0[i] = s.d0[i - 1] | nE[i];
+    // (position 1 of row 1: D1[0] = 0, so the OR falls away)
+    n1[1] = bitop3<TT_AND3>(nE[1] & s.d0[1], s.d0[0], n0[0]);
+#pragma unroll
+    for (int i = 2; i < K; ++i)
+        n1[i] = bitop3<TT_AND3>(bitop3<TT_OR_AND>(s.d1[i - 1], nE[i], s.d0[i]), s.d0[i - 1], n0[i - 1]);
+    n2[2] = bitop3<TT_AND3>(nE[2] & s.d1[2], s.d1[1], n1[1]);
+#pragma unroll
+    for (int i = 3; i < K; ++i)
+        n2[i] = bitop3<TT_AND3>(bitop3<TT_OR_AND>(s.d2[i - 1], nE[i], s.d1[i]), s.d1[i - 1], n1[i - 1]);
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        s.d0[i] = n0[i];
+        s.d1[i] = n1[i];
+        s.d2[i] = n2[i];
+    }
+}
+
+// The last position of the three rows: what a base contributes to the window's hits.
+struct Last {
+    uint32_t x0, x1, x2;
+};
+template <int K>
+AC_BS_FN Last last(const State<K>& s) {
+    return Last{s.d0[K - 1], s.d1[K - 1], s.d2[K - 1]};
+}
+// The hits of two bases (the previous base's last positions in `x`) in one AND3 per level: 1.5 ops per base.
+template <int K>
+AC_BS_FN void hits2(State<K>& s, const Last& x) {
+    s.a0 = bitop3<TT_AND3>(s.a0, x.x0, s.d0[K - 1]);
+    s.a1 = bitop3<TT_AND3>(s.a1, x.x1, s.d1[K - 1]);
+    s.a2 = bitop3<TT_AND3>(s.a2, x.x2, s.d2[K - 1]);
+}
+
+// One base with its hits: 3 ops.
+template <int K>
+AC_BS_FN void step(State<K>& s, const uint32_t (&nE)[K]) {
+    advance(s, nE);
+    s.a0 &= s.d0[K - 1];
+    s.a1 &= s.d1[K - 1];
+    s.a2 &= s.d2[K - 1];
+}
+
+// Two bases.
+template <int K>
+AC_BS_FN void step2(State<K>& s, const uint32_t (&nEa)[K], const uint32_t (&nEb)[K]) {
+    advance(s, nEa);
+    const Last x = last(s);
+    advance(s, nEb);
+    hits2(s, x);
+}
+
+// Bit-plane ("vertical") counters: plane b holds bit b of 32 candidates' counts.  A window adds
+// its number of levels hit (0..3) to every candidate at once: the levels nest (a row-d match is one
+// of row d+1), so with h_d = ~a_d the sum h0 + h1 + h2 has low bit h0 ^ h1 ^ h2 and high bit h1; the
+// two bits ripple into the planes.  NPL planes hold counts up to 2^NPL - 1, i.e. VC_WINDOWS
+// windows: the owner flushes (reads every candidate's count with get() and clears) before adding
+// one more.
+constexpr int VC_PLANES = 5;
+constexpr uint32_t VC_WINDOWS = ((1u << VC_PLANES) - 1u) / 3u;  // 10 windows between flushes
+struct VCount {
+    uint32_t p[VC_PLANES];
+    uint32_t n;  // windows added since the last flush (the same in every lane)
+};
+AC_BS_FN void vc_clear(VCount& v) {
+#pragma unroll
+    for (int b = 0; b < VC_PLANES; ++b) v.p[b] = 0u;
+    v.n = 0u;
+}
+AC_BS_FN bool vc_full(const VCount& v) { return v.n >= VC_WINDOWS; }
+// `live`: the candidates' windows that count (a lane without a window adds nothing)
+AC_BS_FN void vc_add(VCount& v, uint32_t a0, uint32_t a1, uint32_t a2, uint32_t live) {
+    const uint32_t lo = ~bitop3<TT_XOR3>(a0, a1, a2) & live;  // (~a0 ^ ~a1 ^ ~a2 = ~(a0 ^ a1 ^ a2))
+    const uint32_t hi = ~a1 & live;
+    const uint32_t c0 = v.p[0] & lo;
+    v.p[0] ^= lo;
+    uint32_t c = bitop3<TT_MAJ>(v.p[1], hi, c0);
+    v.p[1] = bitop3<TT_XOR3>(v.p[1], hi, c0);
+#pragma unroll
+    for (int b = 2; b < VC_PLANES; ++b) {
+        const uint32_t t = v.p[b] & c;
+        v.p[b] ^= c;
+        c = t;
+    }
+    ++v.n;
+}
+AC_BS_FN uint32_t vc_get(const VCount& v, uint32_t j) {
+    uint32_t r = 0;
+#pragma unroll
+    for (int b = 0; b < VC_PLANES; ++b) r |= (v.p[b] >> j & 1u) << b;
+    return r;
+}
+
+}  // namespace bs
+}  // namespace acamd

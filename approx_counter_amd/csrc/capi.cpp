@@ -23,6 +23,7 @@
 #include <thread>
 #include <vector>
 
+#include "bs_nfa.h"
 #include "ctx.h"
 #include "host_pack.h"
 
@@ -254,6 +255,11 @@ ac_status ac_create(ac_ctx** out, int device) {
         for (uint32_t P = 1; P <= AC_MAX_PACK; ++P)
             for (int st = 0; st < 2; ++st)
                 (void)acamd::resident_waves(P, st != 0, ctx->cu_count, &ctx->warm_resident[st][P]);
+        // (the bit-sliced kernels' code with them: their queries load it)
+#define AC_BS_WARM(KK) \
+    for (int st = 0; st < 2; ++st) (void)acamd::resident_waves_bs(KK, st != 0, ctx->cu_count, &ctx->warm_resident_bs[st]);
+        AC_BS_K_LIST(AC_BS_WARM)
+#undef AC_BS_WARM
         ac_ctx::Scratch& sc = ctx->sc[0];
         auto zeroed = [](void** p, size_t bytes) {
             if (hipMalloc(p, bytes) != hipSuccess) return false;

@@ -3,6 +3,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "bs_nfa.h"
 #include "ctx.h"
 #include "nrec.h"
 
@@ -36,6 +37,14 @@ void ensure_warm(ac_ctx* ctx) {
     for (int st = 0; st < 2; ++st)
         for (uint32_t P = 1; P <= AC_MAX_PACK; ++P)
             if (!ctx->resident[st][P]) ctx->resident[st][P] = ctx->warm_resident[st][P];
+    for (int st = 0; st < 2; ++st)
+        if (!ctx->resident_bs[st]) ctx->resident_bs[st] = ctx->warm_resident_bs[st];
+}
+
+// AC_BITSLICE=0 keeps every launch on the word-parallel kernel (A/B runs, the tests of that kernel).
+static bool bitslice_enabled() {
+    static const bool v = env_int("AC_BITSLICE", 1) != 0;
+    return v;
 }
 
 // One fused count launch over `n` device segments.  `err` = the device word
@@ -66,6 +75,13 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
     a.n_segs = n;
     a.m = k;
     a.P = P;
+    // The bit-sliced kernel counts the launch when k is one of its instantiations and
+    // every live segment holds equal windows of 1..256 bases (one slot of the packed image); its
+    // candidate groups are the word-parallel kernel's, its work items rows of windows.
+    bool bs = bitslice_enabled() && acamd::bs::has_k(k) && ulen != nullptr;
+    for (uint32_t i = 0; i < n && bs; ++i)
+        if (segs[i].n_kmers && segs[i].sample.n_windows && (ulen[i] == AC_NO_ULEN || ulen[i] == 0u || ulen[i] > 256u))
+            bs = false;
     uint64_t items = 0;
     for (uint32_t i = 0; i < n; ++i) {
         const ac_segment& s = segs[i];
@@ -84,7 +100,10 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
         if (s.n_kmers && 3ull * s.sample.n_windows >= (1ull << 32))
             return fail(ctx, AC_ERR_INVALID, "a segment of 2^32 / 3 windows or more: its counts would overflow");
         const uint32_t groups = (s.n_kmers + cpw - 1) / cpw;
-        items += (uint64_t)groups * s.sample.n_windows;
+        if (bs)
+            for (uint32_t g = 0; g < groups; ++g) items += acamd::bs_rows(s.n_kmers, g, cpw, s.sample.n_windows);
+        else
+            items += (uint64_t)groups * s.sample.n_windows;
     }
     // Launch plan.  One round of resident waves; work is pulled
     // from dynamic queues: items of `chunk` windows (1 when waves get few
@@ -94,8 +113,10 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
     // to its windows, so every sub-queue holds about the same work.  Workgroups
     // of AC_WAVES_PER_BLOCK waves are dealt round-robin over blocks of that many
     // consecutive sub-queues (one candidate group each).
-    uint32_t& res_p = ctx->resident[staged][P];
-    if (!res_p) AC_HIP(ctx, acamd::resident_waves(P, staged, ctx->cu_count, &res_p));
+    uint32_t& res_p = bs ? ctx->resident_bs[staged] : ctx->resident[staged][P];
+    if (!res_p)
+        AC_HIP(ctx, bs ? acamd::resident_waves_bs(k, staged, ctx->cu_count, &res_p)
+                       : acamd::resident_waves(P, staged, ctx->cu_count, &res_p));
     const uint64_t resident = wave_cap ? std::max<uint64_t>(AC_WAVES_PER_BLOCK, std::min<uint64_t>(wave_cap, res_p) /
                                                                   AC_WAVES_PER_BLOCK * AC_WAVES_PER_BLOCK)
                                        : res_p;
@@ -244,7 +265,9 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
         if (a.seg[i].queue_begin != ~0u && a.seg[i].ulen == AC_NO_ULEN) a.eq = 0u;
     // Live segments' queue_begin values are increasing; the kernel picks the
     // last live segment whose queue_begin <= its sub-queue.
+    a.bs = bs ? 1u : 0u;
     a.total_waves = wave;
+    if (wave) ctx->last_kernel = bs ? 1 : 0;
     ctx->last_waves = wave;
     ctx->last_wpw = wpw;
     ctx->last_groups = groups_total;

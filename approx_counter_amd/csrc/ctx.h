@@ -79,6 +79,8 @@ struct ac_ctx {
     hipEvent_t sub_zero_ev = nullptr;
     // resident waves of the count kernel per pattern pack P (0 = not queried yet)
     uint32_t resident[2][AC_MAX_PACK + 1] = {};  // [staged][P]
+    uint32_t resident_bs[2] = {};                // [staged]: the bit-sliced kernel (queried at its first launch)
+    int last_kernel = -1;  // the count kernel of the context's last launch: 0 word-parallel, 1 bit-sliced
     // last launch geometry
     uint64_t last_waves = 0;
     uint32_t last_wpw = 0, last_groups = 0;
@@ -117,6 +119,7 @@ struct ac_ctx {
     // parsing and exact count instead.
     std::thread warm;
     uint32_t warm_resident[2][AC_MAX_PACK + 1] = {};
+    uint32_t warm_resident_bs[2] = {};
 };
 
 namespace ac_detail {

@@ -904,6 +904,8 @@ ac_status ac_error_count_jobs(ac_ctx* ctx, uint32_t k, const ac_job* jobs, uint3
 
 uint32_t ac_testing_stage_hooks(uint32_t flags) { return g_test_hooks.exchange(flags); }
 
+int ac_testing_last_count_kernel(ac_ctx* ctx) { return ctx ? ctx->last_kernel : -1; }
+
 ac_status ac_error_count_jobs_submit(ac_ctx* ctx, uint32_t k, const ac_job* jobs, uint32_t n_jobs,
                                      uint32_t* d_counts, void* hip_stream) {
     if (ac_status st = check_jobs(ctx, k, jobs, n_jobs)) return st;

@@ -158,11 +158,33 @@ struct LaunchArgs {
     uint32_t eq;  // every live segment has equal windows (ulen), checked on the host to fit its image
     uint32_t m;  // k-mer length
     uint32_t P;  // candidates per lane word
+    uint32_t bs;  // the bit-sliced kernel (bs_count.inc) counts this launch: `chunk` is in rows of windows
 };
 
 inline uint32_t pack_factor(uint32_t k) { return (32u / k) < AC_MAX_PACK ? (32u / k) : AC_MAX_PACK; }
 // candidates per wave of the plain (staged = false) or the early launch's staged kernel
 inline uint32_t cands_per_wave(uint32_t P, bool staged) { return 64u * P * (uint32_t)words_for((int)P, staged); }
+
+// The bit-sliced kernel (bs_count.inc): a candidate group of n candidates (1 .. the
+// group size cands_per_wave(2, *)) takes 1 << bs_lane_shift(n) lanes per window -- one per block of 32
+// candidates, rounded up to a power of two, at least 2 (a row's text is parked in LDS: 32 windows'
+// worth per wave) -- and a wave counts a row of 64 >> bs_lane_shift(n) consecutive windows at once.
+#ifndef BS_WAVES_PER_SIMD
+#define BS_WAVES_PER_SIMD 4  // resident waves per SIMD of the bit-sliced kernel
+#endif
+inline __host__ __device__ uint32_t bs_lane_shift(uint32_t n) {
+    const uint32_t blocks = (n + 31u) / 32u;
+    uint32_t s = 1;
+    while ((1u << s) < blocks) ++s;
+    return s;
+}
+// rows of a segment's group g (of `cpw` candidates, the last one fewer) over n_windows windows
+inline uint64_t bs_rows(uint32_t n_kmers, uint32_t g, uint32_t cpw, uint32_t n_windows) {
+    const uint32_t n = n_kmers - g * cpw < cpw ? n_kmers - g * cpw : cpw;
+    const uint32_t wpr = 64u >> bs_lane_shift(n);
+    return ((uint64_t)n_windows + wpr - 1u) / wpr;
+}
+hipError_t resident_waves_bs(uint32_t k, bool staged, int cu_count, uint32_t* waves);
 
 // Waves of the count kernel for pattern pack P that fit on the device at once.
 hipError_t resident_waves(uint32_t P, bool staged, int cu_count, uint32_t* waves);

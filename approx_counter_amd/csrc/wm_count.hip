@@ -50,6 +50,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bs_nfa.h"
 #include "nrec.h"
 #include "wm_count.h"
 
@@ -1252,7 +1253,18 @@ __device__ __forceinline__ void count_body(const LaunchArgs& a, BlockLds<words_f
     stamp(wave, 3);
 }
 
+#include "bs_count.inc"
+
 }  // namespace
+
+// The bit-sliced kernel (bs_count.inc): k = K, equal windows.  Four waves per SIMD (<= 128 VGPRs),
+// capped by the LDS allocation like the two-word kernel above.
+template <int K, bool STAGED>
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, BS_WAVES_PER_SIMD) void bs_count_kernel(LaunchArgs a) {
+    constexpr int kBlocksPerCu = 4 * BS_WAVES_PER_SIMD / WAVES_PER_BLOCK;
+    __shared__ BsLds<K> lds[(160 * 1024 / kBlocksPerCu) / sizeof(BsLds<K>)];
+    bs_body<K, STAGED>(a, lds[0]);
+}
 
 template <int P, bool STAGED, bool EQ>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, waves_per_simd(words_for(P, STAGED))) void wm2_count_kernel(LaunchArgs a) {
@@ -1308,10 +1320,37 @@ hipError_t resident_waves(uint32_t P, bool staged, int cu_count, uint32_t* waves
 #undef AC_OCC
 }
 
+hipError_t resident_waves_bs(uint32_t k, bool staged, int cu_count, uint32_t* waves) {
+    int blocks = 0;
+    hipError_t e = hipErrorInvalidValue;
+#define AC_BS_OCC(KK)                                                                                             \
+    if (k == KK)                                                                                                  \
+        e = staged ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, bs_count_kernel<KK, true>, 64 * WAVES_PER_BLOCK, 0) \
+                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, bs_count_kernel<KK, false>, 64 * WAVES_PER_BLOCK, 0);
+    AC_BS_K_LIST(AC_BS_OCC)
+#undef AC_BS_OCC
+    if (e != hipSuccess) return e;
+    if (blocks < 1) blocks = 1;
+    *waves = (uint32_t)blocks * WAVES_PER_BLOCK * (uint32_t)cu_count;
+    return hipSuccess;
+}
+
 hipError_t launch_wm2_count(const LaunchArgs& args, hipStream_t stream) {
     if (args.total_waves == 0) return hipSuccess;
     const uint64_t blocks = (args.total_waves + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
     const dim3 grid((uint32_t)blocks), block(64 * WAVES_PER_BLOCK);
+    if (args.bs) {  // the bit-sliced kernel (the host routes only equal-window launches of a listed k to it)
+        if (!args.eq) return hipErrorInvalidValue;
+#define AC_BS_LAUNCH(KK)                                                                            \
+    if (args.m == KK) {                                                                             \
+        if (args.staged) hipLaunchKernelGGL((bs_count_kernel<KK, true>), grid, block, 0, stream, args); \
+        else hipLaunchKernelGGL((bs_count_kernel<KK, false>), grid, block, 0, stream, args);        \
+        return hipGetLastError();                                                                   \
+    }
+        AC_BS_K_LIST(AC_BS_LAUNCH)
+#undef AC_BS_LAUNCH
+        return hipErrorInvalidValue;
+    }
 #define AC_LAUNCH(PP)                                                                            \
     case PP:                                                                                     \
         if (args.staged && args.eq)                                                              \

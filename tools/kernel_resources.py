@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-kernel register use and spills of the count kernels (wm2_count_kernel instantiations), from the
+"""Per-kernel register use and spills of the count kernels (wm2_count_kernel and bs_count_kernel instantiations), from the
 compiler's kernel-resource-usage remarks.
 
     python3 tools/kernel_resources.py [wm_count.hip] [-- extra hipcc flags]
@@ -37,7 +37,7 @@ def resources(src, extra=()):
                            text=True).stdout.split("\n")
     for r, n in zip(rows, names):
         r["name"] = n.replace("acamd::(anonymous namespace)::", "")
-    return [r for r in rows if "wm2_count_kernel" in r["name"]]
+    return [r for r in rows if "wm2_count_kernel" in r["name"] or "bs_count_kernel" in r["name"]]
 
 
 def main():

@@ -44,7 +44,10 @@ def main():
     ap.add_argument("--workload", required=True)
     ap.add_argument("--valu", help="directory of a SQ_INSTS_VALU pass (optional)")
     ap.add_argument("--out", required=True)
+    ap.add_argument("--kernel", default=KERNEL,
+                    help="substring of the kernel's name (bs_count_kernel: the bit-sliced kernel, DESIGN.md 4e)")
     a = ap.parse_args()
+    globals()["KERNEL"] = a.kernel
     fetch, nf = mean_counter(a.fetch, "FETCH_SIZE")
     write, nw = mean_counter(a.write, "WRITE_SIZE")
     d = {"workload": a.workload, "kernel": KERNEL, "fetch_size_kb": fetch, "write_size_kb": write,
