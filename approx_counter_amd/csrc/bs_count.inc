@@ -89,7 +89,8 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
     const uint32_t wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint64_t wave = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wib;
     stamp(wave, 0);
-    // The deal of workgroups to block-queues, the sub-queues and the staging wait are count_body's.
+    // The deal of workgroups to block-queues, the sub-queues and the staging wait are count_body's
+    // (wgs_of: the workgroups dealt to a block-queue, which the count hand-off waits for).
     const uint32_t nqb = a.n_queues / WAVES_PER_BLOCK;
     const uint32_t blocks = (uint32_t)(a.total_waves / WAVES_PER_BLOCK);
     const uint32_t rank = blockIdx.x / nqb;
@@ -164,8 +165,8 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
     uint32_t ulen = sg.ulen;
     asm volatile("" : "+s"(ulen));
     const uint32_t sbytes = ((ulen + 31u) & ~31u) >> 2;  // bytes of a window's slot of code words (8..64)
-    uint32_t seg_nw = sg.n_windows, seg_chunk = sg.chunk, seg_qb = sg.queue_begin;
-    asm volatile("" : "+s"(seg_nw), "+s"(seg_chunk), "+s"(seg_qb));
+    uint32_t seg_nw = sg.n_windows, seg_chunk = sg.chunk;
+    asm volatile("" : "+s"(seg_nw), "+s"(seg_chunk));
     uint32_t st_codes_off = STAGED ? sg.stage_codes_off : 0u, st_nchunks = STAGED ? sg.stage_chunks : 0u;
     uint32_t* st_gen = STAGED ? sg.stage_gen : nullptr;
     if constexpr (STAGED) asm volatile("" : "+s"(st_codes_off), "+s"(st_nchunks), "+s"(st_gen));
@@ -185,19 +186,17 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
             __hip_atomic_exchange(&a.queue[((a.bank ^ 1u) * (uint64_t)a.qstride + z) * AC_QUEUE_LINE], 0u,
                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 
-    // Dynamic work queues (count_body): items of `chunk` rows, strided over the group's sub-queues; a
-    // wave's first item is static, further ones are claimed one row ahead, then stolen from siblings.
+    // Dynamic work queues (count_body's layout): items of `chunk` rows, strided over the group's
+    // sub-queues.  Every item is claimed from the wave's sub-queue counter, the first one too (no static
+    // first item: a wave that starts late takes what is left then, DESIGN.md §4e), further ones one row
+    // ahead; a wave whose sub-queue is empty steals from its siblings'.
     const uint32_t S = sg.subq;
     const uint32_t chunk = seg_chunk;
     const uint32_t n_items = (n_rows + chunk - 1u) / chunk;
     uint32_t jc = j;
     auto counter = [&](uint32_t jj) { return g_queue + (uint64_t)jj * AC_QUEUE_LINE; };
-    auto waves_in = [&](uint32_t jj) {
-        const uint32_t qq = seg_qb + g * S + jj;
-        return wgs_of(qq / WAVES_PER_BLOCK);
-    };
     auto n_in = [&](uint32_t jj) { return jj < n_items ? (n_items - jj + S - 1u) / S : 0u; };
-    uint32_t jc_waves = waves_in(jc), jc_items = n_in(jc);
+    uint32_t jc_items = n_in(jc);
     auto item_of = [&](uint32_t c) { return c < jc_items ? jc + c * S : n_items; };
     auto dequeue_issue = [&]() -> uint32_t {
         uint32_t v = 0;
@@ -212,7 +211,7 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
                 if (lane < 63u && b + lane < S) {
                     const uint32_t jj = (j + b + lane) % S;
                     const uint32_t v = __hip_atomic_load(counter(jj), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    have = waves_in(jj) + v < n_in(jj);
+                    have = v < n_in(jj);
                 }
                 const uint64_t mk = __ballot(have);
                 if (mk) found = b + (uint32_t)__builtin_ctzll(mk);
@@ -220,9 +219,8 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
             if (found == S) return n_items;
             const uint32_t jj = (j + found) % S;
             jc = jj;
-            jc_waves = waves_in(jj);
             jc_items = n_in(jj);
-            const uint32_t c = jc_waves + __builtin_amdgcn_readfirstlane(dequeue_issue());
+            const uint32_t c = __builtin_amdgcn_readfirstlane(dequeue_issue());
             if (c < jc_items) return item_of(c);
         }
     };
@@ -296,8 +294,9 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
         __builtin_amdgcn_wave_barrier();
     };
 
-    uint32_t item = (j < n_items && !skip) ? item_of(rank) : n_items;
-    uint32_t row = item * chunk, item_end = min(n_rows, row + chunk);
+    // The first item's claim goes out here and is read after the table barrier.
+    const uint32_t pending0 = skip ? 0u : dequeue_issue();
+    uint32_t item = n_items, row = 0u, item_end = 0u;
 
     // The workgroup's ~Eq table: wave v takes candidates 64 v .. 64 v + 63 of the group (blocks 2 v and
     // 2 v + 1), one ballot per (position, character); lane 4 i + c keeps the ballot of position i and
@@ -329,14 +328,16 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
         for (uint32_t x = lane; x < BS_GROUP; x += 64u) lds.cnt[x] = 0u;
     }
     bool stage_ok = true;
-    if (item < n_items) {  // (before the table barrier only the plain kernel: a staged wave waiting for
-                           // its first row must not hold its workgroup's other waves there)
-        if (!STAGED) fetch_row(row, buf);
-    }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     stamp(wave, 1);
-    if (STAGED && item < n_items) {
-        stage_ok = gate(row);
+    if (!skip) {
+        item = __builtin_amdgcn_readfirstlane(item_of(__builtin_amdgcn_readfirstlane(pending0)));
+        if (item >= n_items && S > 1) item = __builtin_amdgcn_readfirstlane(steal());
+    }
+    row = item * chunk;
+    item_end = min(n_rows, row + chunk);
+    if (item < n_items) {
+        if (STAGED) stage_ok = gate(row);
         if (stage_ok) fetch_row(row, buf);
         else item = n_items;
     }
@@ -432,7 +433,7 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
             if (__builtin_expect(q == q_claim && last, 0)) pending = dequeue_issue();
             if (__builtin_expect(q == q_next, 0)) {  // (unlikely: the register allocator keeps the NFA state in registers around the blocks, not around this)
                 if (last) {
-                    nitem = __builtin_amdgcn_readfirstlane(item_of(jc_waves + __builtin_amdgcn_readfirstlane(pending)));
+                    nitem = __builtin_amdgcn_readfirstlane(item_of(__builtin_amdgcn_readfirstlane(pending)));
                     if (nitem >= n_items && S > 1) nitem = __builtin_amdgcn_readfirstlane(steal());
                     nrow = nitem * chunk;
                 }

@@ -47,6 +47,19 @@ static bool bitslice_enabled() {
     return v;
 }
 
+// Waves of a bit-sliced launch of `items` row items, of `resident` that fit at once: a
+// launch of more than one and at most 1.25 rounds (measured at 1.05 and 1.22; at 1.5 and 2.0 rounds the
+// step is no shorter or longer) takes 3 of every 4 resident workgroups.  A SIMD's
+// issue slots are filled by three of these waves; the fourth one is starved through its table build
+// and reaches its first row when the others finish theirs, so in a short launch it is the tail.
+// AC_BS_WAVES_PCT (1..100) sets the share for every bit-sliced launch instead, for A/B runs.
+static uint64_t bs_launch_waves(uint64_t items, uint64_t resident) {
+    static const int pct = env_int("AC_BS_WAVES_PCT", 0);
+    const uint64_t want = pct > 0 ? resident * (uint64_t)std::min(pct, 100) / 100
+                                  : (items > resident && 4 * items <= 5 * resident) ? resident * 3 / 4 : resident;
+    return std::max<uint64_t>(AC_WAVES_PER_BLOCK, want / AC_WAVES_PER_BLOCK * AC_WAVES_PER_BLOCK);
+}
+
 // One fused count launch over `n` device segments.  `err` = the device word
 // the kernel reports skipped windows in (the context's, for ac_check, when NULL).
 // `sc` = the scratch set (one per concurrently running stream); `wave_cap` (0
@@ -117,9 +130,10 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
     if (!res_p)
         AC_HIP(ctx, bs ? acamd::resident_waves_bs(k, staged, ctx->cu_count, &res_p)
                        : acamd::resident_waves(P, staged, ctx->cu_count, &res_p));
-    const uint64_t resident = wave_cap ? std::max<uint64_t>(AC_WAVES_PER_BLOCK, std::min<uint64_t>(wave_cap, res_p) /
+    const uint64_t fit = wave_cap ? std::max<uint64_t>(AC_WAVES_PER_BLOCK, std::min<uint64_t>(wave_cap, res_p) /
                                                                   AC_WAVES_PER_BLOCK * AC_WAVES_PER_BLOCK)
-                                       : res_p;
+                                  : res_p;
+    const uint64_t resident = bs ? bs_launch_waves(items, fit) : fit;
     const uint32_t wpw = (uint32_t)std::max<uint64_t>(1, (items + resident - 1) / resident);
 #ifdef AC_FORCE_CHUNK  // A/B builds (tools/variants.sh): fixed item size
     const uint32_t chunk = AC_FORCE_CHUNK;
