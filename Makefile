@@ -52,7 +52,11 @@ all: $(LIB) $(HOSTLIB) $(CLI) oracle
 
 lib: $(LIB)
 
-$(OBJDIR)/wm_count.o: $(CSRC)/wm_count.hip $(CSRC)/wm_tid_blocks.inc $(CSRC)/wm_window_loop.inc $(CSRC)/bs_count.inc $(HDRS)
+# the count kernels' translation unit: wm_count.hip and the files it includes
+WM_SRC := $(CSRC)/wm_count.hip $(CSRC)/wm_tid_blocks.inc $(CSRC)/stage_dev.inc $(CSRC)/count_frame.inc \
+	$(CSRC)/wm_window_loop.inc $(CSRC)/bs_count.inc
+
+$(OBJDIR)/wm_count.o: $(WM_SRC) $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) -c $< -o $@
 
@@ -90,7 +94,7 @@ $(CLI): $(HOSTDIR)/adaptfinder.cpp $(HOST_SRC) $(HOST_HDRS) $(LIB)
 oracle:
 	$(MAKE) -s -C oracle
 
-asm: $(CSRC)/wm_count.hip $(CSRC)/wm_tid_blocks.inc $(CSRC)/wm_window_loop.inc $(CSRC)/bs_count.inc $(HDRS)
+asm: $(WM_SRC) $(HDRS)
 	@mkdir -p build/asm
 	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) --cuda-device-only -S $< -o build/asm/wm_count.s
 

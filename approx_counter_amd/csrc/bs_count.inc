@@ -1,6 +1,7 @@
-// bs_count.inc -- the bit-sliced count kernel (DESIGN.md §4e), included by wm_count.hip inside its
-// anonymous namespace: it shares that file's staging protocol (stage_copy, stage_copy_dp, stage_gate),
-// work queues' layout and count hand-off, and differs in how a wave maps onto the work.
+// bs_count.inc -- the bit-sliced count kernel's body (DESIGN.md §4e), included by wm_count.hip inside
+// its anonymous namespace: the NFA's place in the frame of count_frame.inc (deal, staged prologue,
+// sub-queues, gate, count hand-off -- the word-parallel kernel's), with another mapping of a wave
+// onto the work.
 //
 // Mapping: bit j of a lane word is candidate j of a block of 32 (bs_nfa.h); a candidate group
 // (BS_GROUP candidates, the host's cands_per_wave, so the launch plan, the acc slots and the groups'
@@ -89,69 +90,18 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
     const uint32_t wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint64_t wave = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wib;
     stamp(wave, 0);
-    // The deal of workgroups to block-queues, the sub-queues and the staging wait are count_body's
-    // (wgs_of: the workgroups dealt to a block-queue, which the count hand-off waits for).
-    const uint32_t nqb = a.n_queues / WAVES_PER_BLOCK;
-    const uint32_t blocks = (uint32_t)(a.total_waves / WAVES_PER_BLOCK);
-    const uint32_t rank = blockIdx.x / nqb;
-    auto shift = [&](uint32_t r) { return (r + (r >> 3) * 4u) % nqb; };
-    const uint32_t bq = (blockIdx.x % nqb + shift(rank)) % nqb;
-    auto wgs_of = [&](uint32_t qb) {
-        return blocks / nqb + ((qb + nqb - shift(blocks / nqb)) % nqb < blocks % nqb ? 1u : 0u);
-    };
-    const uint32_t q = bq * WAVES_PER_BLOCK + wib;
-    int si = 0;
-#pragma unroll
-    for (int i = 1; i < AC_MAX_SEGS; ++i)
-        if (i < (int)a.n_segs && q >= a.seg[i].queue_begin) si = i;
+    const Deal deal = deal_of(a);
+    const Place pl = place_of(a, deal.bq, wib);
+    const int si = pl.si;
     const SegDev& sg = a.seg[si];
-    const uint32_t ql = q - sg.queue_begin;
-    const uint32_t g = ql / sg.subq, j = ql % sg.subq;
+    const uint32_t g = pl.g, j = pl.j;
 
-    uint32_t has_n = sg.has_n;
+    Gate gt;  // staged: while the segment is not known complete, rows go through the gate
+    gt.has_n = sg.has_n;
     bool skip = false;
-    bool partial = false;  // staged: the segment is not known complete; rows go through the gate
-    uint32_t v_lo = 0, v_hi = 0;
-    uint32_t* st_words = nullptr;
-    if (STAGED && sg.stage_chunks) {
-        st_words = a.stage + AC_STAGE_L_SEG(si) * AC_QUEUE_LINE;
-        const uint32_t pre_bytes = sg.stage_codes_off;
-        if (blockIdx.x < a.copier_wgs) {  // copier workgroup: every wave serves every segment's tickets
-            for (uint32_t i2 = 0; i2 < a.n_segs; ++i2) {
-                const uint32_t s2 = (blockIdx.x + i2) % a.n_segs;
-                const SegDev& c2 = a.seg[s2];
-                if (!c2.stage_chunks) continue;
-#ifndef AC_NO_DEVICE_PACK
-                const bool ok = c2.dp_src
-                                    ? stage_copy_dp(c2, a.stage + AC_STAGE_L_SEG(s2) * AC_QUEUE_LINE, a.gen, a.err)
-                                    : stage_copy(c2.stage_src, c2.stage_dst, c2.stage_chunks,
-                                                 c2.stage_codes_off / AC_STAGE_CHUNK, a.host_hdr + s2 * AC_QUEUE_LINE,
-                                                 a.stage + AC_STAGE_L_SEG(s2) * AC_QUEUE_LINE, c2.stage_gen, a.gen, s2);
-#else
-                const bool ok = stage_copy(c2.stage_src, c2.stage_dst, c2.stage_chunks, c2.stage_codes_off / AC_STAGE_CHUNK,
-                                           a.host_hdr + s2 * AC_QUEUE_LINE, a.stage + AC_STAGE_L_SEG(s2) * AC_QUEUE_LINE,
-                                           c2.stage_gen, a.gen, s2);
-#endif
-                if (!__builtin_amdgcn_readfirstlane((uint32_t)ok))
-                    if (lane == 0) atomicOr(a.err, AC_DEVERR_STAGE);
-            }
-        }
-        if (wib == 0) {
-            uint32_t r = ~0u;
-            if (!a.copier_wgs) {
-                if (lane == 0) atomicOr(a.err, AC_DEVERR_STAGE);
-            } else {  // only the k-mers (the ~Eq table) are needed before counting starts
-                r = (uint32_t)stage_gate(st_words, sg.stage_gen, sg.stage_chunks, blockIdx.x % AC_STAGE_REPL, a.gen, 0u,
-                                         8u * sg.n_kmers, a.err, pre_bytes);
-            }
-            if (lane == 0) lds.stage_r = r;
-            stamp(wave, 7);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        const uint32_t r = __builtin_amdgcn_readfirstlane(lds.stage_r);
-        skip = r == ~0u;
-        partial = r == 2u;
-        has_n = (skip || partial) ? 0u : r;
+    if (STAGED && sg.stage_chunks) {  // (every segment has equal windows: never the whole-segment wait)
+        gt.words = a.stage + AC_STAGE_L_SEG(si) * AC_QUEUE_LINE;
+        skip = gt.open(staged_prologue(a, sg, gt.words, wib, lane, wave, &lds.stage_r));
     }
     const uint32_t* codes_p = sg.codes;
     const uint32_t* nmask_p = sg.nmask;
@@ -161,15 +111,13 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
     const __amdgpu_buffer_rsrc_t r_codes = __builtin_amdgcn_make_buffer_rsrc((void*)codes_p, 0, (int)code_bytes, 0x00020000);
     // (the N bitmap is read only by windows that need it, and -- staged -- only once the segment is complete)
     const __amdgpu_buffer_rsrc_t r_nmask = __builtin_amdgcn_make_buffer_rsrc((void*)nmask_p, 0, (int)nmask_bytes, 0x00020000);
-    uint32_t* g_queue = a.queue + ((uint64_t)a.bank * a.qstride + sg.queue_begin + g * sg.subq) * AC_QUEUE_LINE;
+    uint32_t* g_queue = group_counters(a, sg, g);
     uint32_t ulen = sg.ulen;
     asm volatile("" : "+s"(ulen));
     const uint32_t sbytes = ((ulen + 31u) & ~31u) >> 2;  // bytes of a window's slot of code words (8..64)
     uint32_t seg_nw = sg.n_windows, seg_chunk = sg.chunk;
     asm volatile("" : "+s"(seg_nw), "+s"(seg_chunk));
-    uint32_t st_codes_off = STAGED ? sg.stage_codes_off : 0u, st_nchunks = STAGED ? sg.stage_chunks : 0u;
-    uint32_t* st_gen = STAGED ? sg.stage_gen : nullptr;
-    if constexpr (STAGED) asm volatile("" : "+s"(st_codes_off), "+s"(st_nchunks), "+s"(st_gen));
+    if constexpr (STAGED) gt.pin(sg);
     const bool rec = sg.nrec != 0u;  // inline N records (nrec.h) in the top bits of every slot's last code word
     const uint32_t rec_pb = nrec_pos_bits(ulen);
 
@@ -180,75 +128,26 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
     const uint32_t lane_off = blk * 16u;
     const uint32_t n_rows = (seg_nw + wpr - 1u) >> (6u - lwsh);
 
-    // Counters of the other queue bank are zeroed for the next launch.
-    for (uint64_t z = wave; z < a.zero_count; z += a.total_waves)
-        if (lane == 0)
-            __hip_atomic_exchange(&a.queue[((a.bank ^ 1u) * (uint64_t)a.qstride + z) * AC_QUEUE_LINE], 0u,
-                                  __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    zero_other_bank(a, wave, lane);
 
-    // Dynamic work queues (count_body's layout): items of `chunk` rows, strided over the group's
-    // sub-queues.  Every item is claimed from the wave's sub-queue counter, the first one too (no static
-    // first item: a wave that starts late takes what is left then, DESIGN.md §4e), further ones one row
-    // ahead; a wave whose sub-queue is empty steals from its siblings'.
+    // The group's work queues (SubQueues): items of `chunk` rows.  Every item is claimed from the
+    // wave's sub-queue counter, the first one too (no static first item: a wave that starts late takes
+    // what is left then, DESIGN.md §4e), further ones one row ahead.
     const uint32_t S = sg.subq;
     const uint32_t chunk = seg_chunk;
     const uint32_t n_items = (n_rows + chunk - 1u) / chunk;
-    uint32_t jc = j;
-    auto counter = [&](uint32_t jj) { return g_queue + (uint64_t)jj * AC_QUEUE_LINE; };
-    auto n_in = [&](uint32_t jj) { return jj < n_items ? (n_items - jj + S - 1u) / S : 0u; };
-    uint32_t jc_items = n_in(jc);
-    auto item_of = [&](uint32_t c) { return c < jc_items ? jc + c * S : n_items; };
-    auto dequeue_issue = [&]() -> uint32_t {
-        uint32_t v = 0;
-        if (lane == 0) v = __hip_atomic_fetch_add(counter(jc), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return v;
-    };
-    auto steal = [&]() -> uint32_t {
-        for (;;) {
-            uint32_t found = S;
-            for (uint32_t b = 1; b < S && found == S; b += 63u) {
-                bool have = false;
-                if (lane < 63u && b + lane < S) {
-                    const uint32_t jj = (j + b + lane) % S;
-                    const uint32_t v = __hip_atomic_load(counter(jj), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    have = v < n_in(jj);
-                }
-                const uint64_t mk = __ballot(have);
-                if (mk) found = b + (uint32_t)__builtin_ctzll(mk);
-            }
-            if (found == S) return n_items;
-            const uint32_t jj = (j + found) % S;
-            jc = jj;
-            jc_items = n_in(jj);
-            const uint32_t c = __builtin_amdgcn_readfirstlane(dequeue_issue());
-            if (c < jc_items) return item_of(c);
-        }
-    };
+    SubQueues sq = {g_queue, S, n_items, j, lane};
+    sq.serve(j);
 
-    // Staged: the segment is complete (verdict r: 0 / 1) or skipped (~0u).
-    auto completed = [&](uint32_t r) __attribute__((always_inline)) {
-        partial = false;
-        if (r == ~0u) return false;
-        has_n = r;
-        return true;
-    };
     // Staged early counting: before a row's fetch, every byte the fetch reads -- the row's slots, which
     // are contiguous in the image, and the 32 bytes a lane's 16-byte loads may reach past its slot -- is
     // in device memory and inside the N-free prefix; false = skip the segment.
     auto gate = [&](uint32_t rr) __attribute__((always_inline)) {
         if constexpr (STAGED) {
-            if (!partial) return true;
+            if (!gt.partial) return true;
             const uint32_t b0 = rr * wpr * sbytes;
-            const uint32_t r0 = st_codes_off + b0, r1 = st_codes_off + min(b0 + wpr * sbytes + 32u, code_bytes);
-            if (r0 >= v_lo && r1 <= v_hi) return true;
-            const uint64_t gr = stage_gate(st_words, st_gen, st_nchunks, blockIdx.x % AC_STAGE_REPL, a.gen, r0, r1, a.err);
-            const uint32_t r = __builtin_amdgcn_readfirstlane((uint32_t)gr);
-            if (r == 2u) {
-                v_lo = (r0 / AC_STAGE_CHUNK) * AC_STAGE_CHUNK;
-                v_hi = __builtin_amdgcn_readfirstlane((uint32_t)(gr >> 32));
-                return true;
-            }
-            return completed(r);
+            const uint32_t r0 = gt.codes_off + b0, r1 = gt.codes_off + min(b0 + wpr * sbytes + 32u, code_bytes);
+            return gt.pass(r0, r1, a.gen, a.err, [&](uint32_t r) { return gt.completed(r); });
         } else {
             (void)rr;
             return true;
@@ -279,7 +178,7 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
             if (blk == 0u) dst[2] = t2, dst[3] = t3;
         }
         if (blk == 0u) dst[0] = t0, dst[1] = t1;
-        const bool with_n = !rec && has_n;  // no records: every window's N bits are its bitmap words
+        const bool with_n = !rec && gt.has_n;  // no records: every window's N bits are its bitmap words
         if (with_n) {
             const uint32_t noff = off == NO_WINDOW ? NO_WINDOW : off >> 1;
             const bs_v4u n0 = __builtin_amdgcn_raw_buffer_load_b128(r_nmask, noff, 0, 0);
@@ -295,7 +194,7 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
     };
 
     // The first item's claim goes out here and is read after the table barrier.
-    const uint32_t pending0 = skip ? 0u : dequeue_issue();
+    const uint32_t pending0 = skip ? 0u : sq.dequeue_issue();
     uint32_t item = n_items, row = 0u, item_end = 0u;
 
     // The workgroup's ~Eq table: wave v takes candidates 64 v .. 64 v + 63 of the group (blocks 2 v and
@@ -331,8 +230,8 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     stamp(wave, 1);
     if (!skip) {
-        item = __builtin_amdgcn_readfirstlane(item_of(__builtin_amdgcn_readfirstlane(pending0)));
-        if (item >= n_items && S > 1) item = __builtin_amdgcn_readfirstlane(steal());
+        item = __builtin_amdgcn_readfirstlane(sq.item_of(__builtin_amdgcn_readfirstlane(pending0)));
+        if (item >= n_items && S > 1) item = __builtin_amdgcn_readfirstlane(sq.steal());
     }
     row = item * chunk;
     item_end = min(n_rows, row + chunk);
@@ -373,11 +272,10 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
         if (__builtin_expect(__ballot(rc != 0u) != 0ull, 0)) {
             const uint32_t rw = text[(sbytes >> 2) - 1u];
             const bool ovf = has && rc == NREC_OVERFLOW;
-            if (STAGED && partial && __ballot(ovf)) {
-                const uint64_t gr = stage_gate(st_words, st_gen, st_nchunks, blockIdx.x % AC_STAGE_REPL, a.gen, 0u, ~0u, a.err);
-                if (!completed(__builtin_amdgcn_readfirstlane((uint32_t)gr))) stage_ok = false;
+            if (STAGED && gt.partial && __ballot(ovf)) {
+                if (!gt.completed(gt.whole(a.gen, a.err))) stage_ok = false;
             }
-            if (ovf && !has_n) {  // no bitmap for an overflowed record: skipped, reported
+            if (ovf && !gt.has_n) {  // no bitmap for an overflowed record: skipped, reported
                 if (stage_ok) atomicOr(a.err, AC_DEVERR_WINDOW);
                 has = false;
             }
@@ -430,11 +328,11 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
         // CUs ran two rounds while the others idled).
         const uint32_t q_claim = nq > 5u ? nq - 5u : 0u, q_next = nq - 1u;
         for (uint32_t q = 0; q < nq && stage_ok; ++q) {
-            if (__builtin_expect(q == q_claim && last, 0)) pending = dequeue_issue();
+            if (__builtin_expect(q == q_claim && last, 0)) pending = sq.dequeue_issue();
             if (__builtin_expect(q == q_next, 0)) {  // (unlikely: the register allocator keeps the NFA state in registers around the blocks, not around this)
                 if (last) {
-                    nitem = __builtin_amdgcn_readfirstlane(item_of(__builtin_amdgcn_readfirstlane(pending)));
-                    if (nitem >= n_items && S > 1) nitem = __builtin_amdgcn_readfirstlane(steal());
+                    nitem = __builtin_amdgcn_readfirstlane(sq.item_of(__builtin_amdgcn_readfirstlane(pending)));
+                    if (nitem >= n_items && S > 1) nitem = __builtin_amdgcn_readfirstlane(sq.steal());
                     nrow = nitem * chunk;
                 }
                 if (nitem < n_items) {
@@ -467,49 +365,7 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
     if (vc.n) flush();
     stamp(wave, 2);
 
-    // The count hand-off (count_body): one wave adds (1 << 32) + the workgroup's sum into the group's acc
-    // slots; a slot's last workgroup moves the total to the counts.
-    constexpr int Q = (int)(BS_GROUP / 64u);
-    if (STAGED) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (wib == 0) {
-        uint64_t* acc = a.acc + sg.acc_begin + g * BS_GROUP;
-        const uint32_t qb0 = (sg.queue_begin + g * sg.subq) / WAVES_PER_BLOCK, nq = sg.subq / WAVES_PER_BLOCK;
-        uint32_t n_wg = 0;
-        for (uint32_t i = 0; i < nq; ++i) n_wg += wgs_of(qb0 + i);
-        uint32_t mine[Q];
-        uint64_t old[Q];
-#pragma unroll
-        for (int qq = 0; qq < Q; ++qq) {
-            mine[qq] = lds.cnt[qq * 64 + lane];
-            old[qq] = __hip_atomic_fetch_add(&acc[qq * 64 + lane], (1ull << 32) | mine[qq], __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_AGENT);
-        }
-#pragma unroll
-        for (int qq = 0; qq < Q; ++qq) {
-            if ((uint32_t)(old[qq] >> 32) != n_wg - 1u) continue;  // not the slot's last workgroup
-            const uint32_t v = (uint32_t)old[qq] + mine[qq];
-            const uint32_t cand = g * BS_GROUP + (uint32_t)qq * 64u + lane;
-            __hip_atomic_store(&acc[qq * 64 + lane], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (cand < sg.n_kmers) {
-                if (a.add_counts) {
-                    if (v) atomicAdd(&sg.counts[cand], v);
-                } else if (STAGED && a.tag) {
-                    __hip_atomic_store((uint64_t*)sg.counts + cand, ((uint64_t)a.gen << 32) | v, __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_SYSTEM);
-                } else {
-                    sg.counts[cand] = v;
-                }
-            }
-            if (STAGED && qq == 0 && lane == 0) {  // the group's error snapshot (count_body)
-                const uint32_t e = __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (a.tag)
-                    __hip_atomic_store(a.grp_err + sg.group_begin + g, ((uint64_t)a.gen << 32) | e, __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_SYSTEM);
-                else if (e && a.err_out)
-                    atomicOr(a.err_out, e);
-            }
-        }
-    }
+    // The workgroup's sums, slot = candidate of the group (blk * 32 + bit), to the counts.
+    count_hand_off<(int)(BS_GROUP / 64u), STAGED>(a, sg, deal, g, wib, lane, lds.cnt);
     stamp(wave, 3);
 }

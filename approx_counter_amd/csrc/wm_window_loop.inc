@@ -14,9 +14,9 @@ if (STAGED && !GATED) {  // (the first copy's results, made wave-uniform again f
     jc = __builtin_amdgcn_readfirstlane(jc);
     jc_waves = __builtin_amdgcn_readfirstlane(jc_waves);
     jc_items = __builtin_amdgcn_readfirstlane(jc_items);
-    has_n = __builtin_amdgcn_readfirstlane(has_n);
+    gt.has_n = __builtin_amdgcn_readfirstlane(gt.has_n);
 }
-while (item < n_items && (!GATED || partial)) {
+while (item < n_items && (!GATED || gt.partial)) {
     const uint64_t base = nbase;
     const uint32_t len = nlen;
     // Wait for this window's words here, before the next window's fetch is
@@ -41,13 +41,11 @@ while (item < n_items && (!GATED || partial)) {
         if (c == NREC_OVERFLOW) {
             bool have = false;
             if constexpr (STAGED && GATED) {
-                if (partial) {  // wait for the whole segment (its N bitmap)
-                    const uint64_t g = stage_gate(st_words, st_gen, st_nchunks, blockIdx.x % AC_STAGE_REPL,
-                                                  a.gen, 0u, ~0u, a.err);
-                    if (!completed(__builtin_amdgcn_readfirstlane((uint32_t)g))) stage_ok = false;
+                if (gt.partial) {  // wait for the whole segment (its N bitmap)
+                    if (!completed(gt.whole(a.gen, a.err))) stage_ok = false;
                 }
             }
-            if (has_n && stage_ok) {  // this window's N-mask words from the bitmap
+            if (gt.has_n && stage_ok) {  // this window's N-mask words from the bitmap
                 Image full = im;
                 full.nmask = __builtin_amdgcn_make_buffer_rsrc((void*)nmask_p, 0, (int)(uint32_t)(g_nbases >> 3),
                                                                0x00020000);
