@@ -4,29 +4,30 @@
 // onto the work.
 //
 // Mapping: bit j of a lane word is candidate j of a block of 32 (bs_nfa.h); a candidate group
-// (BS_GROUP candidates, the host's cands_per_wave, so the launch plan, the acc slots and the groups'
-// error words are those of the word-parallel kernel) takes LW = max(2, next_pow2(ceil(candidates / 32)))
+// (BS_GROUP candidates for every K, wm_count.h; the host plans the launch, the acc slots and the groups'
+// error words by that size, launch_group_size) takes LW = max(2, next_pow2(ceil(candidates / 32)))
 // lanes per window (bs_lane_shift), lane % LW = the candidate block, and a wave counts a ROW of 64 / LW
 // consecutive windows at once.  A work item is `chunk` rows.
 // Text is per lane: every lane loads its window's slot itself (buffer loads at its own offset, the
 // next row's while this one is counted) and the window's first lane parks it in LDS -- 24 words per
 // window, 16 of codes and 8 of N bits -- from where one code word is read back per 16 bases; per
 // base the lane forms its character (2-bit code + 4 x N bit) and reads nE[0..K-1] for it from the
-// workgroup's ~Eq table in LDS with K / 4 ds_read_b128.
-// Table layout: [character 0..7][quad 0..K/4-1][block 0..BS_LWMAX-1] x 16 B, the characters BS_ROW
+// workgroup's ~Eq table in LDS with ceil(K / 4) ds_read_b128.
+// Table layout: [character 0..7][quad 0..ceil(K/4)-1][block 0..BS_LWMAX-1] x 16 B (the last quad's
+// positions past K - 1 are padding of the table, never written or used: the pattern is not padded --
+// leading wildcard positions would change the counts), the characters BS_ROW
 // bytes further apart than their quads need, so that characters of different parity start in
 // different bank halves (windows of one ds_read_b128 lane group that hold the same character read
 // one address).  Characters 4..7 (an N base, whatever its code bits) are all ones, as are the bits
 // of candidate slots past n_kmers.
-// Only equal-window launches (every live segment has ulen in 1..256) with K in AC_BS_K_LIST.
-constexpr uint32_t BS_GROUP = 64u * 2u * (uint32_t)words_for(2, false);  // = cands_per_wave(2, *)
-static_assert(words_for(2, false) == words_for(2, true), "one group size for plain and staged launches");
+// Only equal-window launches (every live segment has ulen in 1..256) with K in AC_BS_K_LIST; the
+// residency of an instantiation is bs_waves_per_simd(K) (wm_count.h).
 constexpr uint32_t BS_LWMAX = BS_GROUP / 32u;       // lanes per window of a full group
 constexpr uint32_t BS_ROW = BS_LWMAX * 16u;         // bytes of one (character, quad) table row
 
 template <int K>
 struct BsLds {
-    static constexpr uint32_t QUADS = K / 4;
+    static constexpr uint32_t QUADS = (K + 3) / 4;
     static constexpr uint32_t CHAR_STRIDE = (QUADS + 1u) * BS_ROW;
     alignas(16) uint32_t tab[8u * CHAR_STRIDE / 4u];  // characters 4..7: an N base, whatever its code bits
     uint32_t cnt[BS_GROUP];
@@ -39,17 +40,17 @@ struct BsLds {
 typedef uint32_t bs_v4u __attribute__((ext_vector_type(4)));
 
 // nE[0..K-1] of this lane's block for the character whose table row starts at byte `addr`
-// (character * CHAR_STRIDE + block * 16): K / 4 ds_read_b128 at immediate offsets.
+// (character * CHAR_STRIDE + block * 16): ceil(K / 4) ds_read_b128 at immediate offsets.
 template <int K>
 __device__ __forceinline__ void bs_read(const BsLds<K>& lds, uint32_t addr, uint32_t (&e)[K]) {
     const char* p = (const char*)lds.tab + addr;
 #pragma unroll
-    for (int q = 0; q < K / 4; ++q) {
+    for (int q = 0; q < (K + 3) / 4; ++q) {
         const bs_v4u v = *(const bs_v4u*)(p + q * BS_ROW);
         e[4 * q] = v.x;
-        e[4 * q + 1] = v.y;
-        e[4 * q + 2] = v.z;
-        e[4 * q + 3] = v.w;
+        if (4 * q + 1 < K) e[4 * q + 1] = v.y;
+        if (4 * q + 2 < K) e[4 * q + 2] = v.z;
+        if (4 * q + 3 < K) e[4 * q + 3] = v.w;
     }
 }
 
@@ -84,7 +85,7 @@ __device__ __forceinline__ void bs_block4(bs::State<K>& s, const BsLds<K>& lds, 
 
 template <int K, bool STAGED>
 __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
-    static_assert(K % 4 == 0 && K <= 32, "the table is read in quads of positions; a k-mer is one 64-bit word");
+    static_assert(K >= 3 && K <= 32, "a k-mer is one 64-bit word (dna2int layout: K = 32 fills it)");
     constexpr uint32_t CS = BsLds<K>::CHAR_STRIDE;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -198,28 +199,31 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
     uint32_t item = n_items, row = 0u, item_end = 0u;
 
     // The workgroup's ~Eq table: wave v takes candidates 64 v .. 64 v + 63 of the group (blocks 2 v and
-    // 2 v + 1), one ballot per (position, character); lane 4 i + c keeps the ballot of position i and
-    // character c and stores its two halves.  Wave 0 also writes the N rows and zeroes the counts.
+    // 2 v + 1), one ballot per (position, character), in passes of 16 positions: lane 4 (i % 16) + c
+    // keeps the ballot of position i and character c and stores its two halves after the pass.  Wave 0
+    // also writes the N rows and zeroes the counts.
     if (!skip && (wib == 0 || 2u * wib < LW)) {
         const uint32_t c = g * BS_GROUP + wib * 64u + lane;
         const bool have = wib * 64u + lane < ng;
         const uint64_t km = have ? sg.kmers[c] : 0ull;
-        uint64_t mine = ~0ull;
 #pragma unroll
-        for (uint32_t i = 0; i < (uint32_t)K; ++i) {
-            const uint32_t ch = (uint32_t)(km >> (2u * ((uint32_t)K - 1u - i))) & 3u;
+        for (uint32_t i0 = 0; i0 < (uint32_t)K; i0 += 16u) {
+            uint64_t mine = ~0ull;
 #pragma unroll
-            for (uint32_t cc = 0; cc < 4u; ++cc) {
-                const uint64_t bal = __ballot(!have || ch != cc);
-                if (lane == 4u * i + cc) mine = bal;
+            for (uint32_t i = i0; i < i0 + 16u && i < (uint32_t)K; ++i) {
+                const uint32_t ch = (uint32_t)(km >> (2u * ((uint32_t)K - 1u - i))) & 3u;
+#pragma unroll
+                for (uint32_t cc = 0; cc < 4u; ++cc) {
+                    const uint64_t bal = __ballot(!have || ch != cc);
+                    if (lane == 4u * (i - i0) + cc) mine = bal;
+                }
             }
-        }
-        static_assert(4 * K <= 64, "one lane per (position, character)");
-        if (lane < 4u * (uint32_t)K) {
-            const uint32_t i = lane >> 2, cc = lane & 3u;
-            uint32_t* p = lds.tab + (cc * CS + (i >> 2) * BS_ROW + (i & 3u) * 4u) / 4u;
-            p[(2u * wib) * 4u] = (uint32_t)mine;
-            if (2u * wib + 1u < BS_LWMAX) p[(2u * wib + 1u) * 4u] = (uint32_t)(mine >> 32);
+            const uint32_t i = i0 + (lane >> 2), cc = lane & 3u;  // (one lane per (position, character) of the pass)
+            if (i < (uint32_t)K) {
+                uint32_t* p = lds.tab + (cc * CS + (i >> 2) * BS_ROW + (i & 3u) * 4u) / 4u;
+                p[(2u * wib) * 4u] = (uint32_t)mine;
+                if (2u * wib + 1u < BS_LWMAX) p[(2u * wib + 1u) * 4u] = (uint32_t)(mine >> 32);
+            }
         }
     }
     if (wib == 0) {

@@ -21,13 +21,21 @@
 #else
 #define AC_BS_FN inline
 #endif
+#if defined(__clang__)
+#define AC_BS_UNROLL _Pragma("unroll")
+#else
+#define AC_BS_UNROLL  // (the host build's compiler may not know the pragma)
+#endif
 
 namespace acamd {
 namespace bs {
 
-// The instantiated pattern lengths, in one place (count_launch.cpp routes by it, bs_count.inc
-// instantiates by it).
-#define AC_BS_K_LIST(X) X(16)
+// The instantiated pattern lengths, in one place (the host's bs_launch routes by it, wm_count.hip
+// instantiates by it, tools/bs_nfa_check.cpp runs by it): 16 and 18..32.  k = 15 and k = 17 stay on the
+// word-parallel kernel (tests pin them there); below 16 that kernel packs 2-4 candidates per lane
+// word and is not the slower one.
+#define AC_BS_K_LIST(X) \
+    X(16) X(18) X(19) X(20) X(21) X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(29) X(30) X(31) X(32)
 constexpr bool has_k(uint32_t k) {
 #define AC_BS_K_EQ(KK) || k == KK
     return false AC_BS_K_LIST(AC_BS_K_EQ);
@@ -60,7 +68,7 @@ struct State {
 
 template <int K>
 AC_BS_FN void init(State<K>& s) {
-#pragma unroll
+    AC_BS_UNROLL
     for (int i = 0; i < K; ++i) {
         s.d0[i] = ~0u;
         s.d1[i] = i >= 1 ? ~0u : 0u;
@@ -78,18 +86,18 @@ AC_BS_FN void advance(State<K>& s, const uint32_t (&nE)[K]) {
     n1[0] = 0u;
     n2[0] = 0u;
     n2[1] = 0u;
-#pragma unroll
+    AC_BS_UNROLL
     for (int i = 1; i < K; ++i) n0[i] = s.d0[i - 1] | nE[i];
     // (position 1 of row 1: D1[0] = 0, so the OR falls away)
     n1[1] = bitop3<TT_AND3>(nE[1] & s.d0[1], s.d0[0], n0[0]);
-#pragma unroll
+    AC_BS_UNROLL
     for (int i = 2; i < K; ++i)
         n1[i] = bitop3<TT_AND3>(bitop3<TT_OR_AND>(s.d1[i - 1], nE[i], s.d0[i]), s.d0[i - 1], n0[i - 1]);
     n2[2] = bitop3<TT_AND3>(nE[2] & s.d1[2], s.d1[1], n1[1]);
-#pragma unroll
+    AC_BS_UNROLL
     for (int i = 3; i < K; ++i)
         n2[i] = bitop3<TT_AND3>(bitop3<TT_OR_AND>(s.d2[i - 1], nE[i], s.d1[i]), s.d1[i - 1], n1[i - 1]);
-#pragma unroll
+    AC_BS_UNROLL
     for (int i = 0; i < K; ++i) {
         s.d0[i] = n0[i];
         s.d1[i] = n1[i];
@@ -144,7 +152,7 @@ struct VCount {
     uint32_t n;  // windows added since the last flush (the same in every lane)
 };
 AC_BS_FN void vc_clear(VCount& v) {
-#pragma unroll
+    AC_BS_UNROLL
     for (int b = 0; b < VC_PLANES; ++b) v.p[b] = 0u;
     v.n = 0u;
 }
@@ -157,7 +165,7 @@ AC_BS_FN void vc_add(VCount& v, uint32_t a0, uint32_t a1, uint32_t a2, uint32_t 
     v.p[0] ^= lo;
     uint32_t c = bitop3<TT_MAJ>(v.p[1], hi, c0);
     v.p[1] = bitop3<TT_XOR3>(v.p[1], hi, c0);
-#pragma unroll
+    AC_BS_UNROLL
     for (int b = 2; b < VC_PLANES; ++b) {
         const uint32_t t = v.p[b] & c;
         v.p[b] ^= c;
@@ -167,7 +175,7 @@ AC_BS_FN void vc_add(VCount& v, uint32_t a0, uint32_t a1, uint32_t a2, uint32_t 
 }
 AC_BS_FN uint32_t vc_get(const VCount& v, uint32_t j) {
     uint32_t r = 0;
-#pragma unroll
+    AC_BS_UNROLL
     for (int b = 0; b < VC_PLANES; ++b) r |= (v.p[b] >> j & 1u) << b;
     return r;
 }

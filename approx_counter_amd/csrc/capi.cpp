@@ -255,11 +255,10 @@ ac_status ac_create(ac_ctx** out, int device) {
         for (uint32_t P = 1; P <= AC_MAX_PACK; ++P)
             for (int st = 0; st < 2; ++st)
                 (void)acamd::resident_waves(P, st != 0, ctx->cu_count, &ctx->warm_resident[st][P]);
-        // (the bit-sliced kernels' code with them: their queries load it)
-#define AC_BS_WARM(KK) \
-    for (int st = 0; st < 2; ++st) (void)acamd::resident_waves_bs(KK, st != 0, ctx->cu_count, &ctx->warm_resident_bs[st]);
-        AC_BS_K_LIST(AC_BS_WARM)
-#undef AC_BS_WARM
+        // (the bit-sliced kernels' code with them: the k = 16 queries load the code object; another
+        // k is queried at its first launch, so start-up does not grow with AC_BS_K_LIST)
+        for (int st = 0; st < 2; ++st)
+            (void)acamd::resident_waves_bs(16u, st != 0, ctx->cu_count, &ctx->warm_resident_bs[st][16]);
         ac_ctx::Scratch& sc = ctx->sc[0];
         auto zeroed = [](void** p, size_t bytes) {
             if (hipMalloc(p, bytes) != hipSuccess) return false;
@@ -710,7 +709,8 @@ ac_status ac_host_alloc(size_t bytes, void** out) {
     *out = nullptr;
     HostBlock b;
     b.n = bytes ? bytes : 16;
-    hipError_t e = hipHostMalloc((void**)&b.h, b.n, hipHostMallocDefault);
+    // (to a 4-byte boundary: the device packer reads a block in whole dwords, stage_pack_chunk)
+    hipError_t e = hipHostMalloc((void**)&b.h, (b.n + 3) & ~size_t(3), hipHostMallocDefault);
     if (e != hipSuccess) return hip_fail(nullptr, e, "hipHostMalloc");
     e = hipHostGetDevicePointer((void**)&b.d, b.h, 0);
     if (e != hipSuccess) {

@@ -6,6 +6,7 @@
 #include "bs_nfa.h"
 #include "ctx.h"
 #include "nrec.h"
+#include "stage_plan.h"
 
 namespace ac_detail {
 
@@ -38,13 +39,8 @@ void ensure_warm(ac_ctx* ctx) {
         for (uint32_t P = 1; P <= AC_MAX_PACK; ++P)
             if (!ctx->resident[st][P]) ctx->resident[st][P] = ctx->warm_resident[st][P];
     for (int st = 0; st < 2; ++st)
-        if (!ctx->resident_bs[st]) ctx->resident_bs[st] = ctx->warm_resident_bs[st];
-}
-
-// AC_BITSLICE=0 keeps every launch on the word-parallel kernel (A/B runs, the tests of that kernel).
-static bool bitslice_enabled() {
-    static const bool v = env_int("AC_BITSLICE", 1) != 0;
-    return v;
+        for (uint32_t kk = 0; kk <= 32; ++kk)
+            if (!ctx->resident_bs[st][kk]) ctx->resident_bs[st][kk] = ctx->warm_resident_bs[st][kk];
 }
 
 // Waves of a bit-sliced launch of `items` row items, of `resident` that fit at once: a
@@ -52,19 +48,22 @@ static bool bitslice_enabled() {
 // step is no shorter or longer) takes 3 of every 4 resident workgroups.  A SIMD's
 // issue slots are filled by three of these waves; the fourth one is starved through its table build
 // and reaches its first row when the others finish theirs, so in a short launch it is the tail.
+// That was measured at four waves per SIMD and holds for the kernels of that residency (k = 16) only:
+// the wider patterns' kernels, at 2-3 waves per SIMD, launch every resident workgroup.
 // AC_BS_WAVES_PCT (1..100) sets the share for every bit-sliced launch instead, for A/B runs.
-static uint64_t bs_launch_waves(uint64_t items, uint64_t resident) {
+static uint64_t bs_launch_waves(uint32_t k, uint64_t items, uint64_t resident) {
     static const int pct = env_int("AC_BS_WAVES_PCT", 0);
+    const bool three_of_four = acamd::bs_waves_per_simd((int)k) == 4 && items > resident && 4 * items <= 5 * resident;
     const uint64_t want = pct > 0 ? resident * (uint64_t)std::min(pct, 100) / 100
-                                  : (items > resident && 4 * items <= 5 * resident) ? resident * 3 / 4 : resident;
+                                  : three_of_four ? resident * 3 / 4 : resident;
     return std::max<uint64_t>(AC_WAVES_PER_BLOCK, want / AC_WAVES_PER_BLOCK * AC_WAVES_PER_BLOCK);
 }
 
 // One fused count launch over `n` device segments.  `err` = the device word
 // the kernel reports skipped windows in (the context's, for ac_check, when NULL).
-// `sc` = the scratch set (one per concurrently running stream); `wave_cap` (0
-// = none) limits the launch to that many waves, so another launch's waves can
-// be resident beside it.
+// `sc` = the scratch set (one per concurrently running stream); `wave_div` (0, 1
+// = none) limits the launch to 1 / wave_div of its kernel's resident waves, so another
+// launch's waves can be resident beside it.
 // `no_n` (optional, per segment): the segment's image is known to hold no N.
 // `ulen` (optional, per segment): AC_NO_ULEN, or all windows have this length
 // and sit back to back at ceil32(ulen)-base strides (start / length unread).
@@ -73,7 +72,7 @@ static uint64_t bs_launch_waves(uint64_t items, uint64_t resident) {
 // segment's region from src (the pinned block) to dst once the host flags it in
 // host_hdr, and reports its completion there.
 ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hipStream_t stream, bool zero,
-                 uint32_t* err, int scratch, uint64_t wave_cap, const bool* no_n, const uint32_t* ulen,
+                 uint32_t* err, int scratch, uint32_t wave_div, const bool* no_n, const uint32_t* ulen,
                  const StageLaunch* stage, const bool* nrec) {
     ensure_warm(ctx);
     ac_ctx::Scratch& sc = ctx->sc[scratch];
@@ -82,19 +81,19 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
     if (n && !segs) return fail(ctx, AC_ERR_INVALID, "segments is NULL");
     const uint32_t P = acamd::pack_factor(k);
     const bool staged = stage != nullptr;
-    const uint32_t cpw = acamd::cands_per_wave(P, staged);
     acamd::LaunchArgs a;
     std::memset(&a, 0, sizeof a);
     a.n_segs = n;
     a.m = k;
     a.P = P;
     // The bit-sliced kernel counts the launch when k is one of its instantiations and
-    // every live segment holds equal windows of 1..256 bases (one slot of the packed image); its
-    // candidate groups are the word-parallel kernel's, its work items rows of windows.
-    bool bs = bitslice_enabled() && acamd::bs::has_k(k) && ulen != nullptr;
-    for (uint32_t i = 0; i < n && bs; ++i)
-        if (segs[i].n_kmers && segs[i].sample.n_windows && (ulen[i] == AC_NO_ULEN || ulen[i] == 0u || ulen[i] > 256u))
-            bs = false;
+    // every live segment holds equal windows of 1..256 bases (one slot of the packed image): decided
+    // once (bs_launch, as the jobs stage's plan decided it), with the size of the launch's candidate
+    // groups; its work items are rows of windows.
+    bool live[AC_MAX_SEGS];
+    for (uint32_t i = 0; i < n; ++i) live[i] = segs[i].n_kmers && segs[i].sample.n_windows;
+    const bool bs = acamd::bs_launch(k, n, live, ulen);
+    const uint32_t cpw = acamd::launch_group_size(k, staged, bs);
     uint64_t items = 0;
     for (uint32_t i = 0; i < n; ++i) {
         const ac_segment& s = segs[i];
@@ -126,14 +125,14 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
     // to its windows, so every sub-queue holds about the same work.  Workgroups
     // of AC_WAVES_PER_BLOCK waves are dealt round-robin over blocks of that many
     // consecutive sub-queues (one candidate group each).
-    uint32_t& res_p = bs ? ctx->resident_bs[staged] : ctx->resident[staged][P];
+    uint32_t& res_p = bs ? ctx->resident_bs[staged][k] : ctx->resident[staged][P];
     if (!res_p)
         AC_HIP(ctx, bs ? acamd::resident_waves_bs(k, staged, ctx->cu_count, &res_p)
                        : acamd::resident_waves(P, staged, ctx->cu_count, &res_p));
-    const uint64_t fit = wave_cap ? std::max<uint64_t>(AC_WAVES_PER_BLOCK, std::min<uint64_t>(wave_cap, res_p) /
-                                                                  AC_WAVES_PER_BLOCK * AC_WAVES_PER_BLOCK)
-                                  : res_p;
-    const uint64_t resident = bs ? bs_launch_waves(items, fit) : fit;
+    const uint64_t fit = wave_div > 1 ? std::max<uint64_t>(AC_WAVES_PER_BLOCK, res_p / wave_div / AC_WAVES_PER_BLOCK *
+                                                                                   AC_WAVES_PER_BLOCK)
+                                      : res_p;
+    const uint64_t resident = bs ? bs_launch_waves(k, items, fit) : fit;
     const uint32_t wpw = (uint32_t)std::max<uint64_t>(1, (items + resident - 1) / resident);
 #ifdef AC_FORCE_CHUNK  // A/B builds (tools/variants.sh): fixed item size
     const uint32_t chunk = AC_FORCE_CHUNK;

@@ -79,7 +79,8 @@ struct ac_ctx {
     hipEvent_t sub_zero_ev = nullptr;
     // resident waves of the count kernel per pattern pack P (0 = not queried yet)
     uint32_t resident[2][AC_MAX_PACK + 1] = {};  // [staged][P]
-    uint32_t resident_bs[2] = {};                // [staged]: the bit-sliced kernel (queried at its first launch)
+    uint32_t resident_bs[2][33] = {};            // [staged][k]: the bit-sliced kernel for k (16: queried by the
+                                                 // warm-up; another k at its first launch)
     int last_kernel = -1;  // the count kernel of the context's last launch: 0 word-parallel, 1 bit-sliced
     // last launch geometry
     uint64_t last_waves = 0;
@@ -119,7 +120,7 @@ struct ac_ctx {
     // parsing and exact count instead.
     std::thread warm;
     uint32_t warm_resident[2][AC_MAX_PACK + 1] = {};
-    uint32_t warm_resident_bs[2] = {};
+    uint32_t warm_resident_bs[2][33] = {};
 };
 
 namespace ac_detail {
@@ -175,7 +176,7 @@ uint32_t stage_copiers(uint64_t tickets);
 // Joins ac_create's warm-up thread (once) and takes the resident-wave counts it queried.
 void ensure_warm(ac_ctx* ctx);
 ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hipStream_t stream,
-                 bool zero, uint32_t* err = nullptr, int scratch = 0, uint64_t wave_cap = 0,
+                 bool zero, uint32_t* err = nullptr, int scratch = 0, uint32_t wave_div = 0,
                  const bool* no_n = nullptr, const uint32_t* ulen = nullptr, const StageLaunch* stage = nullptr,
                  const bool* nrec = nullptr);
 

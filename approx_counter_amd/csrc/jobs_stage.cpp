@@ -671,14 +671,8 @@ ac_status run_dma(const StageCall& c, const std::vector<Task>& tasks, const Slot
     make_segs(c.jobs, p, m, c.d_counts, segs);
     // the synchronous path reads the error word back with the counts; a
     // submit reports through the context's word (ac_check)
-    uint64_t cap = 0;
-    if (c.wave_div > 1) {
-        const uint32_t P = acamd::pack_factor(c.k);
-        if (!ctx->resident[0][P]) AC_HIP(ctx, acamd::resident_waves(P, false, ctx->cu_count, &ctx->resident[0][P]));
-        cap = ctx->resident[0][P] / c.wave_div;
-    }
     if (ac_status st = launch(ctx, c.k, segs, p.n, c.stream, c.zero, c.d_counts ? nullptr : (uint32_t*)(m.hd + p.off_err),
-                              p.scratch, cap, no_n, p.ulen, nullptr, p.nrec))
+                              p.scratch, c.wave_div, no_n, p.ulen, nullptr, p.nrec))
         return st;
     clk.mark(PH_LAUNCH_ENQ);
     clk.mark(PH_D2H_ENQ);

@@ -195,7 +195,12 @@ __device__ __forceinline__ void stage_pack_chunk(const uint8_t* src, const uint6
     pc.cap = nrec_cap(ulen);
     pc.pb = nrec_pos_bits(ulen);
     const uint32_t w0 = pc.cw_lo / pc.SW, w1 = min(n_windows, (pc.cw_hi + pc.SW - 1u) / pc.SW);
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, (int)src_bytes, 0x00020000);
+    // (the range check is per dword: a dword that holds the block's last bytes and reaches past them
+    // would read as zero and the last window lose up to 3 bases, so the range ends at the next 4-byte
+    // boundary of the block -- ac_host_alloc allocates up to there; the bytes past a window are masked)
+    const uint32_t mis = (uint32_t)(uintptr_t)src & 3u;
+    const __amdgpu_buffer_rsrc_t rs =
+        __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, (int)(((src_bytes + mis + 3u) & ~3u) - mis), 0x00020000);
     const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void*)offs, 0, (int)(n_windows * 8u), 0x00020000);
     pc.rc = __builtin_amdgcn_make_buffer_rsrc((void*)codes_dst, 0, (int)code_bytes, 0x00020000);
     pc.rn = __builtin_amdgcn_make_buffer_rsrc((void*)nmask_dst, 0, (int)(code_bytes / 2u), 0x00020000);

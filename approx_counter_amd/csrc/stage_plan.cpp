@@ -3,12 +3,29 @@
 #include "stage_plan.h"
 
 #include <algorithm>
+#include <cstdlib>
 
 #include "approx_counter_amd_testing.h"
+#include "bs_nfa.h"
 #include "host_pack.h"
 #include "wm_count.h"
 
 namespace acamd {
+
+bool bs_launch(uint32_t k, uint32_t n, const bool* live, const uint32_t* ulen) {
+    static const bool enabled = [] {
+        const char* e = std::getenv("AC_BITSLICE");
+        return !e || !*e || std::atoi(e) != 0;
+    }();
+    if (!enabled || !bs::has_k(k) || !ulen) return false;
+    for (uint32_t i = 0; i < n; ++i)
+        if (live[i] && (ulen[i] == AC_NO_ULEN || ulen[i] == 0u || ulen[i] > 256u)) return false;
+    return true;
+}
+
+uint32_t launch_group_size(uint32_t k, bool staged, bool bs) {
+    return bs ? BS_GROUP : cands_per_wave(pack_factor(k), staged);
+}
 
 int stage_parts(uint64_t total_w) {
     return total_w >= STAGE_PARTS4_MIN_WINDOWS ? 4 : total_w >= STAGE_PARTS2_MIN_WINDOWS ? 2 : 1;
@@ -151,7 +168,10 @@ void layout_block(uint32_t k, const ac_job* jobs, JobPlan& p, bool have_d_counts
     p.off_gerr = off;
     p.n_gerr = 0;
     if (p.tag) {
-        const uint32_t cpw = cands_per_wave(pack_factor(k), true);  // (tagged: a staged launch)
+        // (tagged: a staged launch; the kernel is the one launch() will pick for these jobs)
+        bool live[AC_MAX_JOBS];
+        for (uint32_t j = 0; j < p.n; ++j) live[j] = jobs[j].n_kmers && p.hi[j] > p.lo[j];
+        const uint32_t cpw = launch_group_size(k, true, bs_launch(k, p.n, live, p.ulen));
         for (uint32_t j = 0; j < p.n; ++j)
             if (jobs[j].n_kmers && p.hi[j] > p.lo[j]) p.n_gerr += (jobs[j].n_kmers + cpw - 1) / cpw;
         off = align256(off + sizeof(uint64_t) * p.n_gerr);
@@ -199,8 +219,8 @@ std::vector<Task> plan_stage(uint32_t k, const ac_job* jobs, JobPlan& p, bool ha
                              uint64_t min_task_windows, int early_mode, uint32_t hooks, BlockRunner run_blocks) {
     std::vector<Task> tasks = cut_tasks(jobs, p, pool_participants, min_task_windows);
     scan_spans(jobs, p, tasks, pool_participants, run_blocks);
+    window_forms(p, tasks);  // (before the layout: the groups' error words depend on the kernel, that on ulen)
     layout_block(k, jobs, p, have_d_counts);
-    window_forms(p, tasks);
     if (p.early) early_regions(p, early_mode, hooks);
     return tasks;
 }

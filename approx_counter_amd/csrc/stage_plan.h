@@ -86,6 +86,16 @@ uint32_t part_cut(const uint32_t* length, uint32_t n, double frac);
 // (equal shares of the bases).
 std::vector<std::vector<uint32_t>> part_cuts(const ac_job* jobs, uint32_t n_jobs, int parts);
 
+// Which count kernel a launch runs on, decided once for the plan and the launch: the
+// bit-sliced kernel counts it when k is in AC_BS_K_LIST, every live segment (one with candidates and
+// windows: live[i]) holds equal windows of 1..256 bases (ulen[i]; ulen NULL = none does), and
+// AC_BITSLICE is not 0 (A/B runs, the tests of the word-parallel kernel).
+bool bs_launch(uint32_t k, uint32_t n, const bool* live, const uint32_t* ulen);
+// Candidates of such a launch's candidate groups: BS_GROUP for a bit-sliced launch, else the
+// word-parallel kernel's candidates per wave.  Everything counted per group goes by it: the work
+// items, the acc slots, the sub-queues, a tagged launch's group error words and their polling.
+uint32_t launch_group_size(uint32_t k, bool staged, bool bs);
+
 // run(n, fn): fn(b) for every b in [0, n), on the caller's worker pool.
 using BlockRunner = void (*)(uint32_t n, const std::function<void(uint32_t)>& fn);
 // A span scan of more windows than this goes through the BlockRunner, when there is one.

@@ -88,11 +88,11 @@ struct SegDev {
     uint64_t n_bases;     // image size (bases); windows outside it are skipped
     uint32_t n_kmers;
     uint32_t n_windows;
-    uint32_t groups;      // candidate groups of cands_per_wave(P) candidates
+    uint32_t groups;      // candidate groups of the launch's group size (cands_per_wave(P), bit-sliced: BS_GROUP)
     uint32_t chunk;       // windows per work item of the dynamic queues
     uint32_t queue_begin; // index of this segment's first sub-queue (groups x subq of them)
     uint32_t subq;        // sub-queues per candidate group (proportional to n_windows; a multiple of AC_WAVES_PER_BLOCK)
-    uint32_t acc_begin;   // this segment's first slot in LaunchArgs::acc (groups x cands_per_wave slots)
+    uint32_t acc_begin;   // this segment's first slot in LaunchArgs::acc (groups x group size slots)
     uint32_t group_begin;  // launch-wide index of this segment's first candidate group (LaunchArgs::grp_err)
     uint32_t has_n;       // 0: the image holds no N (its N bitmap is not read; every word reads as 0)
     uint32_t ulen;        // AC_NO_ULEN, or every window has this length and window w starts at base
@@ -166,12 +166,28 @@ inline uint32_t pack_factor(uint32_t k) { return (32u / k) < AC_MAX_PACK ? (32u 
 inline uint32_t cands_per_wave(uint32_t P, bool staged) { return 64u * P * (uint32_t)words_for((int)P, staged); }
 
 // The bit-sliced kernel (bs_count.inc): a candidate group of n candidates (1 .. the
-// group size cands_per_wave(2, *)) takes 1 << bs_lane_shift(n) lanes per window -- one per block of 32
+// group size BS_GROUP) takes 1 << bs_lane_shift(n) lanes per window -- one per block of 32
 // candidates, rounded up to a power of two, at least 2 (a row's text is parked in LDS: 32 windows'
 // worth per wave) -- and a wave counts a row of 64 >> bs_lane_shift(n) consecutive windows at once.
+// Its candidate groups hold BS_GROUP candidates whatever k is: for k = 16 that is the word-parallel
+// kernel's group (cands_per_wave(2, *)), for k >= 17 (P = 1) it is not -- the host sizes a launch's
+// groups with launch_group_size (stage_plan.h).
+constexpr uint32_t BS_GROUP = 64u * 2u * (uint32_t)words_for(2, false);
+static_assert(words_for(2, false) == words_for(2, true), "one group size for plain and staged launches");
 #ifndef BS_WAVES_PER_SIMD
-#define BS_WAVES_PER_SIMD 4  // resident waves per SIMD of the bit-sliced kernel
+#define BS_WAVES_PER_SIMD 4  // resident waves per SIMD of the bit-sliced kernel for k = 16
 #endif
+#ifndef BS_WAVES_PER_SIMD_MID
+#define BS_WAVES_PER_SIMD_MID 3  // ... for k = 18..BS_K_MID
+#endif
+#ifndef BS_K_MID
+#define BS_K_MID 23  // (k = 24: the staged kernel spills VGPRs inside the NFA block at 3 waves)
+#endif
+// Resident waves per SIMD of the bit-sliced kernel for pattern length k: the NFA state is 3 k
+// registers and a base's table rows 2 k more, so the wider instantiations run at the highest residency
+// whose register budget holds them without scratch access inside the 4-base block.
+// Both __launch_bounds__ and the LDS allocation that caps residency take it from here.
+constexpr int bs_waves_per_simd(int k) { return k <= 16 ? BS_WAVES_PER_SIMD : k <= BS_K_MID ? BS_WAVES_PER_SIMD_MID : 2; }
 inline __host__ __device__ uint32_t bs_lane_shift(uint32_t n) {
     const uint32_t blocks = (n + 31u) / 32u;
     uint32_t s = 1;

@@ -51,7 +51,7 @@
 // One translation unit, in files (map: DESIGN.md §4): here the word-parallel body (count_body; loop in
 // wm_window_loop.inc, NFA blocks in wm_tid_blocks.inc), the two __global__ kernels and their dispatch;
 // stage_dev.inc the staged launch's device side; count_frame.inc what the bodies share (deal, gate,
-// count hand-off); bs_count.inc the bit-sliced body (k = 16, equal windows).
+// count hand-off); bs_count.inc the bit-sliced body (k in AC_BS_K_LIST, equal windows).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -634,11 +634,12 @@ __device__ __forceinline__ void count_body(const LaunchArgs& a, BlockLds<words_f
 
 }  // namespace
 
-// The bit-sliced kernel (bs_count.inc): k = K, equal windows.  Four waves per SIMD (<= 128 VGPRs),
-// capped by the LDS allocation like the two-word kernel above.
+// The bit-sliced kernel (bs_count.inc): k = K, equal windows.  bs_waves_per_simd(K) waves per SIMD
+// (K = 16: four, <= 128 VGPRs; wider patterns fewer), capped by the LDS allocation like the two-word
+// kernel below.
 template <int K, bool STAGED>
-__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, BS_WAVES_PER_SIMD) void bs_count_kernel(LaunchArgs a) {
-    constexpr int kBlocksPerCu = 4 * BS_WAVES_PER_SIMD / WAVES_PER_BLOCK;
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, bs_waves_per_simd(K)) void bs_count_kernel(LaunchArgs a) {
+    constexpr int kBlocksPerCu = 4 * bs_waves_per_simd(K) / WAVES_PER_BLOCK;
     __shared__ BsLds<K> lds[(160 * 1024 / kBlocksPerCu) / sizeof(BsLds<K>)];
     bs_body<K, STAGED>(a, lds[0]);
 }

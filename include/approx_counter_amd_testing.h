@@ -38,8 +38,8 @@ extern "C" {
 uint32_t ac_testing_stage_hooks(uint32_t flags);
 
 /* Which count kernel the context's last count launch ran: 0 the word-parallel kernel
- * (wm2_count_kernel), 1 the bit-sliced kernel (bs_count_kernel: k = 16, equal windows of at most
- * 256 bases, unless AC_BITSLICE=0); -1 before the first launch.  On an ac_create_multi context:
+ * (wm2_count_kernel), 1 the bit-sliced kernel (bs_count_kernel: k = 16 or 18..32, every live
+ * segment with equal windows of 1..256 bases, unless AC_BITSLICE=0); -1 before the first launch.  On an ac_create_multi context:
  * shard 0's. */
 int ac_testing_last_count_kernel(ac_ctx* ctx);
 
