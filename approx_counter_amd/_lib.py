@@ -139,6 +139,11 @@ def load():
         L.ac_host_alloc.restype = ctypes.c_int
         L.ac_host_free.argtypes = [vp]
         L.ac_host_free.restype = ctypes.c_int
+    if hasattr(L, "ac_set_max_errors"):  # (an A/B build of an older library lacks the edit budget)
+        L.ac_set_max_errors.argtypes = [vp, ctypes.c_uint32]
+        L.ac_set_max_errors.restype = ctypes.c_int
+        L.ac_max_errors.argtypes = [vp]
+        L.ac_max_errors.restype = ctypes.c_uint32
     L.ac_exact_path.argtypes = [vp]
     L.ac_exact_path.restype = ctypes.c_int
     pint = ctypes.POINTER(ctypes.c_int)

@@ -219,7 +219,8 @@ class ApproxCounter:
     """One device context (ac_create / ac_destroy), or with n_gpus a context
     whose host-buffer counts are sharded over that many devices (ac_create_multi)."""
 
-    def __init__(self, device: int = -1, n_gpus: int = 0):
+    def __init__(self, device: int = -1, n_gpus: int = 0, max_errors: int = 2):
+        """max_errors: the edit budget E of the approximate counts (set_max_errors); 2 is the reference's."""
         L = _lib.load()
         self._L = L
         h = ctypes.c_void_p()
@@ -228,6 +229,29 @@ class ApproxCounter:
         else:
             check(L.ac_create(ctypes.byref(h), device))
         self._h = h
+        if max_errors != 2:
+            try:
+                self.set_max_errors(max_errors)
+            except Exception:
+                self.close()
+                raise
+
+    def set_max_errors(self, max_errors: int) -> None:
+        """ac_set_max_errors: every approximate count of this context from now on adds
+        max(0, E + 1 - d) per window, E = max_errors in 0..3 (2: the reference's contract).  Another
+        budget than 2 counts only where the bit-sliced kernel does -- k = 16 or 18..32, every job with
+        equal windows of 1..256 bases -- and any other call then raises (AC_ERR_INVALID) instead of
+        counting under another budget.  The exact count does not depend on it."""
+        if not hasattr(self._L, "ac_set_max_errors"):
+            raise _lib.ApproxCounterError(_lib.AC_ERR_INVALID, "this build of the library has no ac_set_max_errors")
+        if not 0 <= int(max_errors) <= 3:
+            raise _lib.ApproxCounterError(_lib.AC_ERR_INVALID, "max_errors must be 0..3")
+        check(self._L.ac_set_max_errors(self._h, int(max_errors)), self._h)
+
+    @property
+    def max_errors(self) -> int:
+        """ac_max_errors: the context's edit budget."""
+        return int(self._L.ac_max_errors(self._h)) if hasattr(self._L, "ac_max_errors") else 2
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -482,12 +506,16 @@ def _counter() -> ApproxCounter:
     return _default_counter
 
 
-def error_count(sequences, exact_count, nb_thread: int = 4, k: int = 16, v: int = 0) -> dict:
-    """errorCount (approx_counter.cpp:531-601): {kmer: approximate count}."""
+def error_count(sequences, exact_count, nb_thread: int = 4, k: int = 16, v: int = 0, max_errors: int = 2) -> dict:
+    """errorCount (approx_counter.cpp:531-601): {kmer: approximate count}.  max_errors (an extension:
+    the reference counts at 2): the edit budget of this call, see ApproxCounter.set_max_errors."""
     del nb_thread, v  # OpenMP thread count / verbosity of the CPU reference
     kmers = [int(km) for km, _ in exact_count]
     if not kmers:
         return {}
+    ctr = _counter()
+    if ctr.max_errors != max_errors:
+        ctr.set_max_errors(max_errors)
     # the sample as a StringSet<Dna5String>: packed, sent and counted by ac_error_count_jobs
-    counts = _counter().count_jobs(k, [(np.array(kmers, dtype=np.uint64), Dna5Sample.from_windows(sequences))])[0]
+    counts = ctr.count_jobs(k, [(np.array(kmers, dtype=np.uint64), Dna5Sample.from_windows(sequences))])[0]
     return {km: int(c) for km, c in zip(kmers, counts)}

@@ -1,5 +1,6 @@
-// bs_count.inc -- the bit-sliced count kernel's body (DESIGN.md §4e), included by wm_count.hip inside
-// its anonymous namespace: the NFA's place in the frame of count_frame.inc (deal, staged prologue,
+// bs_count.inc -- the bit-sliced count kernel's body (DESIGN.md §4e), included by wm_count.hip (three NFA
+// rows: edit budgets 0..2) and by bs3_count.hip (four rows: budget 3) inside their anonymous namespaces:
+// the NFA's place in the frame of count_frame.inc (deal, staged prologue,
 // sub-queues, gate, count hand-off -- the word-parallel kernel's), with another mapping of a wave
 // onto the work.
 //
@@ -68,22 +69,50 @@ __device__ __forceinline__ uint32_t bs_row(uint32_t code, uint32_t nm, uint32_t 
 // base's table reads are issued one base ahead.  Bases in pairs: 1.5 ops of hit accumulation per base.
 // One form for windows with and without N: a row of windows has an N in most blocks once some of
 // its windows do.
-template <int K>
-__device__ __forceinline__ void bs_block4(bs::State<K>& s, const BsLds<K>& lds, uint32_t code, uint32_t nm, uint32_t ncode,
+// S: the NFA's state, bs::State<K> (three rows) or bs::StateR<K, R>.  AHEAD2 = false (the widest E = 3
+// kernels, wm_count.h BS3_ONE_BASE_K): one base's table rows are held at a time -- a base's reads are
+// issued when the previous base's rows have been used, K registers less; the SIMD's other wave covers
+// the reads.
+template <int K, bool AHEAD2, class S>
+__device__ __forceinline__ void bs_block4(S& s, const BsLds<K>& lds, uint32_t code, uint32_t nm, uint32_t ncode,
                                           uint32_t nnm, uint32_t lane_off, uint32_t (&ea)[K]) {
+    if constexpr (!AHEAD2) {
+#pragma unroll
+        for (uint32_t b = 0; b < 4u; b += 2u) {
+            bs::advance<K>(s, ea);
+            const auto x = bs::last<K>(s);
+            bs_read<K>(lds, bs_row<K>(code, nm, b + 1u, lane_off), ea);
+            bs::advance<K>(s, ea);
+            bs::hits2<K>(s, x);
+            bs_read<K>(lds, b + 2u < 4u ? bs_row<K>(code, nm, b + 2u, lane_off) : bs_row<K>(ncode, nnm, 0u, lane_off), ea);
+        }
+        return;
+    }
     uint32_t eb[K];
 #pragma unroll
     for (uint32_t b = 0; b < 4u; b += 2u) {
         bs_read<K>(lds, bs_row<K>(code, nm, b + 1u, lane_off), eb);
         bs::advance<K>(s, ea);
-        const bs::Last x = bs::last<K>(s);
+        const auto x = bs::last<K>(s);
         bs_read<K>(lds, b + 2u < 4u ? bs_row<K>(code, nm, b + 2u, lane_off) : bs_row<K>(ncode, nnm, 0u, lane_off), ea);
         bs::advance<K>(s, eb);
         bs::hits2<K>(s, x);
     }
 }
 
-template <int K, bool STAGED>
+// The state of R rows: bs_nfa.h's for the three rows of the E = 2 kernels, else bs_nfa_r.h's.
+template <int K, int R>
+struct BsNfa {
+    typedef bs::StateR<K, R> State;
+};
+template <int K>
+struct BsNfa<K, 3> {
+    typedef bs::State<K> State;
+};
+
+// R = 3: the edit budget E = a.max_errors is 0, 1 or 2 (a smaller budget drops levels where a row's
+// hit masks become counts); R = 4: E = 3.
+template <int K, bool STAGED, int R = 3>
 __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
     static_assert(K >= 3 && K <= 32, "a k-mer is one 64-bit word (dna2int layout: K = 32 fills it)");
     constexpr uint32_t CS = BsLds<K>::CHAR_STRIDE;
@@ -259,6 +288,7 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
     };
 
     const uint32_t nq = (ulen + 3u) >> 2;  // blocks of 4 bases per window
+    const uint32_t budget = a.max_errors;  // (wave-uniform)
     while (item < n_items) {
         const uint32_t* text = &lds.text[wib][buf][wl][0];
         const uint32_t my_off = slot_off(row);
@@ -320,7 +350,7 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
             const uint32_t nmw = row_n ? text[16u + (gc >> 1)] >> ((gc & 1u) * 16u) : 0u;
             return (nmw | (0xffffu << real)) & 0xffffu;
         };
-        bs::State<K> s;
+        typename BsNfa<K, R>::State s;
         bs::init<K>(s);
         uint32_t code = text[0], nm = n_word(0u);
         uint32_t ea[K];
@@ -351,7 +381,7 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
                 ncode = text[(q >> 2) + 1u];
                 nnm = n_word((q >> 2) + 1u);
             }
-            bs_block4<K>(s, lds, code, nm, ncode, nnm, lane_off, ea);
+            bs_block4<K, !(R == 4 && K >= BS3_ONE_BASE_K)>(s, lds, code, nm, ncode, nnm, lane_off, ea);
             code = ncode;
             nm = nnm;
         }
@@ -359,8 +389,13 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
             item = n_items;
             break;
         }
-        bs::vc_add(vc, s.a0, s.a1, s.a2, live);
-        if (bs::vc_full(vc)) flush();
+        if constexpr (R == 3) {
+            bs::vc_add_e(vc, budget, s.a0, s.a1, s.a2, live);
+            if (bs::vc_full(vc)) flush();
+        } else {
+            bs::vc_add_r<R>(vc, s.a, live);
+            if (bs::vc_full_r<R>(vc)) flush();
+        }
         if (last) item_end = min(n_rows, nrow + chunk);
         item = nitem;
         row = nrow;

@@ -26,6 +26,7 @@
 #include "bs_nfa.h"
 #include "ctx.h"
 #include "host_pack.h"
+#include "stage_plan.h"
 
 static_assert(AC_MAX_JOBS <= AC_MAX_SEGS, "every job of ac_error_count_jobs is one segment of one launch");
 
@@ -410,6 +411,11 @@ ac_status count_images_one(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, u
 // contiguous shard per device (balanced by bases), each device counting its
 // shards of all jobs in one fused launch, the shard counts summed on the host.
 ac_status count_images(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, uint32_t n) {
+    // (packed images come with window descriptors: never a bit-sliced launch, so another edit budget
+    // than 2 is refused here, before any copy or shard's launch)
+    if (ctx && ctx->max_errors != 2u)
+        if (const char* why = acamd::budget_refusal(ctx->max_errors, k, 0, nullptr, nullptr))
+            return fail(ctx, AC_ERR_INVALID, why);
     if (!ctx || ctx->peers.empty()) return count_images_one(ctx, k, jobs, n);
     if (ac_status st = check_k(ctx, k)) return st;
     if (n > AC_MAX_JOBS) return fail(ctx, AC_ERR_INVALID, "too many jobs in one call (max 4)");
@@ -604,6 +610,16 @@ ac_status ac_error_count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* j
     return AC_OK;
 }
 
+
+ac_status ac_set_max_errors(ac_ctx* ctx, uint32_t e) {
+    if (!ctx) return fail(nullptr, AC_ERR_INVALID, "ctx is NULL");
+    if (e > 3u) return fail(ctx, AC_ERR_INVALID, "max_errors must be 0..3");
+    ctx->max_errors = e;
+    for (ac_ctx* p : ctx->peers) p->max_errors = e;
+    return AC_OK;
+}
+
+uint32_t ac_max_errors(const ac_ctx* ctx) { return ctx ? ctx->max_errors : 2u; }
 
 ac_status ac_last_launch(const ac_ctx* ctx, uint64_t* waves, uint32_t* windows_per_wave, uint32_t* groups) {
     if (!ctx) return fail(nullptr, AC_ERR_INVALID, "ctx is NULL");

@@ -51,9 +51,10 @@ void ensure_warm(ac_ctx* ctx) {
 // That was measured at four waves per SIMD and holds for the kernels of that residency (k = 16) only:
 // the wider patterns' kernels, at 2-3 waves per SIMD, launch every resident workgroup.
 // AC_BS_WAVES_PCT (1..100) sets the share for every bit-sliced launch instead, for A/B runs.
-static uint64_t bs_launch_waves(uint32_t k, uint64_t items, uint64_t resident) {
+static uint64_t bs_launch_waves(uint32_t k, uint32_t max_errors, uint64_t items, uint64_t resident) {
     static const int pct = env_int("AC_BS_WAVES_PCT", 0);
-    const bool three_of_four = acamd::bs_waves_per_simd((int)k) == 4 && items > resident && 4 * items <= 5 * resident;
+    const bool three_of_four = acamd::bs_waves_per_simd((int)k, max_errors == 3u ? 3 : 2) == 4 && items > resident &&
+                               4 * items <= 5 * resident;
     const uint64_t want = pct > 0 ? resident * (uint64_t)std::min(pct, 100) / 100
                                   : three_of_four ? resident * 3 / 4 : resident;
     return std::max<uint64_t>(AC_WAVES_PER_BLOCK, want / AC_WAVES_PER_BLOCK * AC_WAVES_PER_BLOCK);
@@ -93,6 +94,10 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
     bool live[AC_MAX_SEGS];
     for (uint32_t i = 0; i < n; ++i) live[i] = segs[i].n_kmers && segs[i].sample.n_windows;
     const bool bs = acamd::bs_launch(k, n, live, ulen);
+    // The context's edit budget (ac_set_max_errors): another one than 2 counts on a bit-sliced launch
+    // or not at all -- refused here, before anything is enqueued.
+    const uint32_t E = ctx->max_errors;
+    if (const char* why = acamd::budget_refusal(E, k, n, live, ulen)) return fail(ctx, AC_ERR_INVALID, why);
     const uint32_t cpw = acamd::launch_group_size(k, staged, bs);
     uint64_t items = 0;
     for (uint32_t i = 0; i < n; ++i) {
@@ -107,10 +112,12 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
         if (s.sample.n_bases % 32 || s.sample.n_bases >= AC_MAX_IMAGE_BASES)
             return fail(ctx, AC_ERR_INVALID, "sample n_bases must be a multiple of 32 below 2^34");
         // The count hand-off adds (1 << 32) + sum into 64-bit slots (wm_count.hip): a candidate's sum,
-        // at most 3 per window, must stay below 2^32 or its carry would count as an arrival and the
-        // slot would never see its last workgroup.
-        if (s.n_kmers && 3ull * s.sample.n_windows >= (1ull << 32))
-            return fail(ctx, AC_ERR_INVALID, "a segment of 2^32 / 3 windows or more: its counts would overflow");
+        // at most 3 per window (4 at an edit budget of 3), must stay below 2^32 or its carry would count
+        // as an arrival and the slot would never see its last workgroup.
+        if (s.n_kmers && (E == 3u ? 4ull : 3ull) * s.sample.n_windows >= (1ull << 32))
+            return fail(ctx, AC_ERR_INVALID,
+                        E == 3u ? "a segment of 2^32 / 4 windows or more at max_errors = 3: its counts would overflow"
+                                : "a segment of 2^32 / 3 windows or more: its counts would overflow");
         const uint32_t groups = (s.n_kmers + cpw - 1) / cpw;
         if (bs)
             for (uint32_t g = 0; g < groups; ++g) items += acamd::bs_rows(s.n_kmers, g, cpw, s.sample.n_windows);
@@ -125,14 +132,14 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
     // to its windows, so every sub-queue holds about the same work.  Workgroups
     // of AC_WAVES_PER_BLOCK waves are dealt round-robin over blocks of that many
     // consecutive sub-queues (one candidate group each).
-    uint32_t& res_p = bs ? ctx->resident_bs[staged][k] : ctx->resident[staged][P];
+    uint32_t& res_p = !bs ? ctx->resident[staged][P] : E == 3u ? ctx->resident_bs3[staged][k] : ctx->resident_bs[staged][k];
     if (!res_p)
-        AC_HIP(ctx, bs ? acamd::resident_waves_bs(k, staged, ctx->cu_count, &res_p)
+        AC_HIP(ctx, bs ? acamd::resident_waves_bs(k, staged, ctx->cu_count, &res_p, E == 3u ? 3u : 2u)
                        : acamd::resident_waves(P, staged, ctx->cu_count, &res_p));
     const uint64_t fit = wave_div > 1 ? std::max<uint64_t>(AC_WAVES_PER_BLOCK, res_p / wave_div / AC_WAVES_PER_BLOCK *
                                                                                    AC_WAVES_PER_BLOCK)
                                       : res_p;
-    const uint64_t resident = bs ? bs_launch_waves(k, items, fit) : fit;
+    const uint64_t resident = bs ? bs_launch_waves(k, E, items, fit) : fit;
     const uint32_t wpw = (uint32_t)std::max<uint64_t>(1, (items + resident - 1) / resident);
 #ifdef AC_FORCE_CHUNK  // A/B builds (tools/variants.sh): fixed item size
     const uint32_t chunk = AC_FORCE_CHUNK;
@@ -279,6 +286,7 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
     // Live segments' queue_begin values are increasing; the kernel picks the
     // last live segment whose queue_begin <= its sub-queue.
     a.bs = bs ? 1u : 0u;
+    a.max_errors = E;
     a.total_waves = wave;
     if (wave) ctx->last_kernel = bs ? 1 : 0;
     ctx->last_waves = wave;

@@ -81,6 +81,12 @@ struct ac_ctx {
     uint32_t resident[2][AC_MAX_PACK + 1] = {};  // [staged][P]
     uint32_t resident_bs[2][33] = {};            // [staged][k]: the bit-sliced kernel for k (16: queried by the
                                                  // warm-up; another k at its first launch)
+    uint32_t resident_bs3[2][33] = {};           // the same for the E = 3 kernels (bs3_count.hip), each queried
+                                                 // at its first launch
+    // The edit budget E of the approximate counts (ac_set_max_errors; M1(E): a window adds
+    // max(0, E + 1 - d)): 2 = the reference's.  Another one counts on bit-sliced launches only
+    // (stage_plan.h budget_refusal); on an ac_create_multi context every shard holds the same value.
+    uint32_t max_errors = 2;
     int last_kernel = -1;  // the count kernel of the context's last launch: 0 word-parallel, 1 bit-sliced
     // last launch geometry
     uint64_t last_waves = 0;

@@ -9,6 +9,8 @@
 // Extensions (not in the reference, documented in DESIGN.md):
 //   -g, --gpus N    shard the sampled windows over N GPUs of this node (default 1)
 //   --seed N        seed the read sampling (the reference always uses std::random_device)
+//   --max-errors E  edit budget of the approximate count, 0..3 (the reference hard-codes 2, the default):
+//                   a window adds max(0, E + 1 - d) to a k-mer's count (ac_set_max_errors)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -70,6 +72,10 @@ const Opt OPTS[] = {
     {"o", "out_file", Kind::String, "path to the output file, default is ./out.txt"},
     {"g", "gpus", Kind::Int, "[MI355X build] number of GPUs of this node to shard the count over, default 1"},
     {"", "seed", Kind::Int, "[MI355X build] seed of the read sampling, default: std::random_device"},
+    {"", "max-errors", Kind::Int,
+     "[MI355X build] edit budget E of the approximate count, 0 to 3: a window adds max(0, E + 1 - distance); "
+     "default 2, the reference's. Another value needs a kmer size of 16 or 18 to 32, a sampling length up to 255 "
+     "and one GPU."},
     {"", "host-exact", Kind::Flag,
      "[MI355X build] the reference's host stages: whole reads in memory, exact k-mer count on the CPU"},
     {"", "dump-sample", Kind::String,
@@ -215,7 +221,7 @@ bool write_image(const PackedImage& p, const std::string& path) {
     return std::fclose(f) == 0 && ok;
 }
 
-void open_devices(Devices& dev, uint64_t n_gpus) {
+void open_devices(Devices& dev, uint64_t n_gpus, uint64_t max_errors) {
     if (dev.ctx) return;
     if (n_gpus < 1) n_gpus = 1;
     const int n_dev = ac_device_count();
@@ -223,6 +229,7 @@ void open_devices(Devices& dev, uint64_t n_gpus) {
     if ((int)n_gpus > n_dev)
         std::cerr << "/!\\ WARNING: " << n_gpus << " shards requested on " << n_dev << " visible GPU(s)\n";
     if (ac_create_multi(&dev.ctx, (int)n_gpus) != AC_OK) throw std::runtime_error(ac_last_error(nullptr));
+    if (ac_set_max_errors(dev.ctx, (uint32_t)max_errors) != AC_OK) throw std::runtime_error(ac_last_error(dev.ctx));
     dev.shards = n_gpus;
 }
 
@@ -262,7 +269,7 @@ int main(int argc, char const** argv) {
     uint64_t solid_km = 0, nb_thread = 4, k = 16, sl = 100, sn = 40000, limit = 500, v = 1, nb_of_runs = 1;
     float param_lc = 1.0f, lc = 1.0f;
     bool skip_end = false;
-    uint64_t n_gpus = 1;
+    uint64_t n_gpus = 1, max_errors = 2;
     std::string seed_str;
 
     // Config file (721-737): CLI > config > defaults
@@ -298,6 +305,7 @@ int main(int argc, char const** argv) {
     get_option(args, "multi_run", nb_of_runs);
     get_option(args, "gpus", n_gpus);
     get_option(args, "seed", seed_str);
+    get_option(args, "max-errors", max_errors);
     skip_end = skip_end || args.val.count("skip_end");
     const bool host_exact = args.val.count("host-exact") > 0;
     std::string dump_sample;
@@ -316,6 +324,26 @@ int main(int argc, char const** argv) {
     const std::string warning = "/!\\ WARNING: ", error_pref = "/!\\ ERROR: ";
     if (k < 2 || k > 32) throw std::invalid_argument(error_pref + "kmer size must be between 2 and 32 (included)");
     if (k > sl) throw std::invalid_argument(error_pref + "kmer size must be smaller than the sampling length (k <= sl)");
+    // --max-errors: checked here, before the input is parsed or a device opened.  Another budget than
+    // the reference's counts only on the library's bit-sliced kernel (ac_set_max_errors,
+    // include/approx_counter_amd.h): its k-mer sizes, equal windows of up to 256 bases (an end window is
+    // sl + 1), the sample on one device.
+    if (max_errors > 3) {
+        std::cerr << error_pref << "--max-errors must be 0, 1, 2 or 3" << std::endl;
+        return 1;
+    }
+    if (max_errors != 2) {
+        const char* why = !(k == 16 || (k >= 18 && k <= 32))
+                              ? "--max-errors other than 2 needs a kmer size (-k) of 16 or 18 to 32"
+                          : sl > 255       ? "--max-errors other than 2 needs a sampling length (-sl) of at most 255"
+                          : n_gpus > 1     ? "--max-errors other than 2 needs one GPU (-g 1)"
+                          : host_exact     ? "--max-errors other than 2 cannot be combined with --host-exact"
+                                           : nullptr;
+        if (why) {
+            std::cerr << error_pref << why << std::endl;
+            return 1;
+        }
+    }
     lc = adjust_threshold(param_lc, 16, (uint32_t)k);
 
     if (v > 0) {
@@ -346,10 +374,10 @@ int main(int argc, char const** argv) {
     // the first GPU stage waits for it and reports its failure, if any.
     Devices dev;
     std::future<void> dev_ready;
-    if (dump_sample.empty()) dev_ready = std::async(std::launch::async, [&dev, n_gpus] { open_devices(dev, n_gpus); });
+    if (dump_sample.empty()) dev_ready = std::async(std::launch::async, [&dev, n_gpus, max_errors] { open_devices(dev, n_gpus, max_errors); });
     auto devices = [&]() {
         if (dev_ready.valid()) dev_ready.get();  // rethrows the helper's exception
-        open_devices(dev, n_gpus);
+        open_devices(dev, n_gpus, max_errors);
     };
     if (v > 0) print("Parsing FASTA file", tab_level);
     if (host_exact) read_records(input_file, ids, seqs);

@@ -218,6 +218,23 @@ ac_status check_jobs(ac_ctx* ctx, uint32_t k, const ac_job* jobs, uint32_t n_job
         if (b.sample.n_windows && (!b.sample.bases || !b.sample.offset || !b.sample.length))
             return fail(ctx, AC_ERR_INVALID, "job sample has a NULL array");
     }
+    // An edit budget other than 2 (ac_set_max_errors) counts on bit-sliced launches only.  A call may
+    // become several launches (parts, shards), each of which asks budget_refusal of its own plan; the
+    // whole call is asked first, over every job's whole sample -- whose parts are equal windows when
+    // it is -- so that a call that is refused has launched nothing.
+    if (ctx->max_errors != 2u) {
+        bool live[AC_MAX_JOBS];
+        uint32_t ulen[AC_MAX_JOBS];
+        for (uint32_t j = 0; j < n_jobs; ++j) {
+            const ac_dna5_windows& s = jobs[j].sample;
+            live[j] = jobs[j].n_kmers && s.n_windows;
+            ulen[j] = s.n_windows ? s.length[0] : AC_NO_ULEN;
+            for (uint32_t i = 1; i < s.n_windows && ulen[j] != AC_NO_ULEN; ++i)
+                if (s.length[i] != ulen[j]) ulen[j] = AC_NO_ULEN;
+        }
+        if (const char* why = acamd::budget_refusal(ctx->max_errors, k, n_jobs, live, ulen))
+            return fail(ctx, AC_ERR_INVALID, why);
+    }
     return AC_OK;
 }
 
@@ -698,9 +715,11 @@ ac_status stage_and_launch(ac_ctx* ctx, uint32_t k, const ac_job* jobs, JobPlan&
                            uint32_t* d_counts, int part = 0, uint32_t wave_div = 0, bool zero = true) {
     PhaseClock clk;
     const uint32_t hooks = g_test_hooks.load(std::memory_order_relaxed);
+    p.max_errors = ctx->max_errors;
     std::vector<Task> tasks = acamd::plan_stage(k, jobs, p, d_counts != nullptr, acamd::host_pool().size(), task_windows(),
                                                 stage_early(), hooks, run_on_pool);
     clk.mark(PH_SPAN);
+    if (p.refusal) return fail(ctx, AC_ERR_INVALID, p.refusal);
     if (p.early) {  // the copier workgroups of the launch
         ensure_warm(ctx);
         const uint32_t P = acamd::pack_factor(k);

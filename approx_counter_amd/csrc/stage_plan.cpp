@@ -23,6 +23,23 @@ bool bs_launch(uint32_t k, uint32_t n, const bool* live, const uint32_t* ulen) {
     return true;
 }
 
+const char* budget_refusal(uint32_t max_errors, uint32_t k, uint32_t n, const bool* live, const uint32_t* ulen) {
+    if (max_errors == 2u) return nullptr;
+    if (max_errors > 3u) return "max_errors must be 0..3";
+    if (bs_launch(k, n, live, ulen)) return nullptr;
+    if (!bs::has_k(k)) return "max_errors other than 2 needs k = 16 or 18..32 (the bit-sliced count kernel's lengths)";
+    if (!ulen) return "max_errors other than 2 needs equal windows of 1..256 bases (this launch has ragged windows)";
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!live[i]) continue;
+        if (ulen[i] == AC_NO_ULEN)
+            return "max_errors other than 2 needs equal windows of 1..256 bases in every job of a launch "
+                   "(this launch has ragged windows)";
+        if (ulen[i] == 0u || ulen[i] > 256u)
+            return "max_errors other than 2 needs equal windows of 1..256 bases (this launch's are longer)";
+    }
+    return "max_errors other than 2 needs the bit-sliced count kernel (AC_BITSLICE=0 turns it off)";
+}
+
 uint32_t launch_group_size(uint32_t k, bool staged, bool bs) {
     return bs ? BS_GROUP : cands_per_wave(pack_factor(k), staged);
 }
@@ -220,6 +237,11 @@ std::vector<Task> plan_stage(uint32_t k, const ac_job* jobs, JobPlan& p, bool ha
     std::vector<Task> tasks = cut_tasks(jobs, p, pool_participants, min_task_windows);
     scan_spans(jobs, p, tasks, pool_participants, run_blocks);
     window_forms(p, tasks);  // (before the layout: the groups' error words depend on the kernel, that on ulen)
+    {  // the launch's route decides whether it can count at the plan's edit budget
+        bool live[AC_MAX_JOBS];
+        for (uint32_t j = 0; j < p.n; ++j) live[j] = jobs[j].n_kmers && p.hi[j] > p.lo[j];
+        p.refusal = budget_refusal(p.max_errors, k, p.n, live, p.ulen);
+    }
     layout_block(k, jobs, p, have_d_counts);
     if (p.early) early_regions(p, early_mode, hooks);
     return tasks;

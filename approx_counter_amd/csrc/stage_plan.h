@@ -61,6 +61,10 @@ struct JobPlan {
     // device packing: job j's Dna5 bytes / offsets read by the kernel from pinned memory
     bool dp[AC_MAX_JOBS] = {};
     bool dp_any = false;
+    // the edit budget the launch is to count at (set by the caller; 2 = the reference's), and, from the
+    // plan, why this launch cannot (budget_refusal): the caller then fails the call instead of launching
+    uint32_t max_errors = 2;
+    const char* refusal = nullptr;
 };
 
 // Calls whose pack and DMA take hundreds of
@@ -91,6 +95,11 @@ std::vector<std::vector<uint32_t>> part_cuts(const ac_job* jobs, uint32_t n_jobs
 // windows: live[i]) holds equal windows of 1..256 bases (ulen[i]; ulen NULL = none does), and
 // AC_BITSLICE is not 0 (A/B runs, the tests of the word-parallel kernel).
 bool bs_launch(uint32_t k, uint32_t n, const bool* live, const uint32_t* ulen);
+// The edit budget's question, asked of the same launch by the jobs stage's plan and by the launch: a
+// budget other than 2 counts on bit-sliced launches only (DESIGN.md §4e "Edit budget").  NULL when the
+// launch may run at `max_errors`, else the constraint it breaks, as the text of the caller's error --
+// nothing is launched then: no launch ever counts under another budget than the one asked for.
+const char* budget_refusal(uint32_t max_errors, uint32_t k, uint32_t n, const bool* live, const uint32_t* ulen);
 // Candidates of such a launch's candidate groups: BS_GROUP for a bit-sliced launch, else the
 // word-parallel kernel's candidates per wave.  Everything counted per group goes by it: the work
 // items, the acc slots, the sub-queues, a tagged launch's group error words and their polling.

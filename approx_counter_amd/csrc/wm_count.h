@@ -159,6 +159,8 @@ struct LaunchArgs {
     uint32_t m;  // k-mer length
     uint32_t P;  // candidates per lane word
     uint32_t bs;  // the bit-sliced kernel (bs_count.inc) counts this launch: `chunk` is in rows of windows
+    uint32_t max_errors;  // the edit budget E (0..3) of the counts: a window adds max(0, E + 1 - d); other
+                          // than 2 on bit-sliced launches only (3: the bs3_count.hip kernels)
 };
 
 inline uint32_t pack_factor(uint32_t k) { return (32u / k) < AC_MAX_PACK ? (32u / k) : AC_MAX_PACK; }
@@ -187,7 +189,19 @@ static_assert(words_for(2, false) == words_for(2, true), "one group size for pla
 // registers and a base's table rows 2 k more, so the wider instantiations run at the highest residency
 // whose register budget holds them without scratch access inside the 4-base block.
 // Both __launch_bounds__ and the LDS allocation that caps residency take it from here.
-constexpr int bs_waves_per_simd(int k) { return k <= 16 ? BS_WAVES_PER_SIMD : k <= BS_K_MID ? BS_WAVES_PER_SIMD_MID : 2; }
+// An edit budget of 3 (bs3_count.hip) is a fourth row, 4 k registers of state: 3 waves up to BS3_K_MID, then 2;
+// from BS3_ONE_BASE_K on the block holds one base's table rows at a time instead of two (bs_block4), which
+// is what keeps k = 29..32 at 2 waves without scratch access inside the block (DESIGN.md 4e "Edit budget").
+#ifndef BS3_K_MID
+#define BS3_K_MID 19
+#endif
+#ifndef BS3_ONE_BASE_K
+#define BS3_ONE_BASE_K 29
+#endif
+constexpr int bs_waves_per_simd(int k, int max_errors = 2) {
+    return max_errors == 3 ? (k <= BS3_K_MID ? 3 : 2)
+                           : k <= 16 ? BS_WAVES_PER_SIMD : k <= BS_K_MID ? BS_WAVES_PER_SIMD_MID : 2;
+}
 inline __host__ __device__ uint32_t bs_lane_shift(uint32_t n) {
     const uint32_t blocks = (n + 31u) / 32u;
     uint32_t s = 1;
@@ -200,7 +214,9 @@ inline uint64_t bs_rows(uint32_t n_kmers, uint32_t g, uint32_t cpw, uint32_t n_w
     const uint32_t wpr = 64u >> bs_lane_shift(n);
     return ((uint64_t)n_windows + wpr - 1u) / wpr;
 }
-hipError_t resident_waves_bs(uint32_t k, bool staged, int cu_count, uint32_t* waves);
+hipError_t resident_waves_bs(uint32_t k, bool staged, int cu_count, uint32_t* waves, uint32_t max_errors = 2);
+// bs3_count.hip: the E = 3 kernel for k (AC_BS_K_LIST), plain or staged; nullptr if there is none
+void (*bs3_kernel(uint32_t k, bool staged))(LaunchArgs);
 
 // Waves of the count kernel for pattern pack P that fit on the device at once.
 hipError_t resident_waves(uint32_t P, bool staged, int cu_count, uint32_t* waves);

@@ -56,6 +56,7 @@
 #include <stdint.h>
 
 #include "bs_nfa.h"
+#include "bs_nfa_r.h"
 #include "nrec.h"
 #include "wm_count.h"
 
@@ -656,9 +657,10 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, waves_per_simd(words_for(P, S
 
 namespace {
 // The kernel that counts a launch: word-parallel for pattern pack P (bs_k = 0), or bit-sliced for
-// k = bs_k (AC_BS_K_LIST); nullptr if there is none.
+// k = bs_k (AC_BS_K_LIST) -- at an edit budget of 3 one of bs3_count.hip's; nullptr if there is none.
 typedef void (*CountKernel)(LaunchArgs);
-CountKernel count_kernel(uint32_t P, uint32_t bs_k, bool staged, bool eq) {
+CountKernel count_kernel(uint32_t P, uint32_t bs_k, bool staged, bool eq, uint32_t max_errors = 2u) {
+    if (bs_k && max_errors == 3u) return bs3_kernel(bs_k, staged);
     if (bs_k) {
 #define AC_BS_PICK(KK) \
     if (bs_k == KK) return staged ? bs_count_kernel<KK, true> : bs_count_kernel<KK, false>;
@@ -714,8 +716,8 @@ hipError_t resident_waves(uint32_t P, bool staged, int cu_count, uint32_t* waves
     return occupancy(count_kernel(P, 0u, staged, true), cu_count, waves);
 }
 
-hipError_t resident_waves_bs(uint32_t k, bool staged, int cu_count, uint32_t* waves) {
-    return occupancy(count_kernel(0u, k, staged, true), cu_count, waves);
+hipError_t resident_waves_bs(uint32_t k, bool staged, int cu_count, uint32_t* waves, uint32_t max_errors) {
+    return occupancy(count_kernel(0u, k, staged, true, max_errors), cu_count, waves);
 }
 
 hipError_t launch_wm2_count(const LaunchArgs& args, hipStream_t stream) {
@@ -724,7 +726,10 @@ hipError_t launch_wm2_count(const LaunchArgs& args, hipStream_t stream) {
     const dim3 grid((uint32_t)blocks), block(64 * WAVES_PER_BLOCK);
     // (the bit-sliced kernel: the host routes only equal-window launches of a listed k to it)
     if (args.bs && !(args.eq && args.m)) return hipErrorInvalidValue;
-    const CountKernel kernel = count_kernel(args.P, args.bs ? args.m : 0u, args.staged != 0u, args.eq != 0u);
+    // (and only bit-sliced launches at another edit budget than 2)
+    if (args.max_errors > 3u || (args.max_errors != 2u && !args.bs)) return hipErrorInvalidValue;
+    const CountKernel kernel =
+        count_kernel(args.P, args.bs ? args.m : 0u, args.staged != 0u, args.eq != 0u, args.max_errors);
     if (!kernel) return hipErrorInvalidValue;
     hipLaunchKernelGGL(kernel, grid, block, 0, stream, args);
     return hipGetLastError();

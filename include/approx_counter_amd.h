@@ -410,6 +410,41 @@ int ac_stage_mode(const ac_ctx* ctx);
 ac_status ac_last_launch(const ac_ctx* ctx, uint64_t* waves, uint32_t* windows_per_wave,
                          uint32_t* groups);
 
+/*
+ * The edit budget of the approximate count (an additive export of ABI 8).  The
+ * reference has no counterpart: it hard-codes find<0,2> (approx_counter.cpp:586),
+ * the budget of 2 that stays the default of every context.  With budget E in 0..3
+ * the counting contract is M1(E):
+ *     count = sum over windows w of max(0, E + 1 - d(kmer, w))
+ * with the same d (semi-global Levenshtein distance, a non-ACGT base matching
+ * nothing); E = 2 is M1 above.  Counts stay <= 4 x windows.
+ *
+ * The budget is a property of the context: sticky, applied to every
+ * approximate-count entry point (ac_error_count*, ac_count) from the next call
+ * on, on every shard of an ac_create_multi context; the exact count
+ * (ac_exact_count*) does not depend on it.  Setting it between a submit
+ * (ac_error_count_jobs_submit, ac_error_count_device) and the completion of that
+ * call's stream work is the caller's error, like using two streams at once.
+ *
+ * Where E != 2 runs: only on launches the bit-sliced count kernel takes -- k is 16
+ * or 18..32, every job (segment) that has candidates and windows holds equal
+ * windows of 1..256 bases, and AC_BITSLICE is not 0 in the environment.  That is
+ * every launch of the jobs stage (ac_error_count_jobs / _submit) over equal read
+ * ends at those k, ac_error_count_device with window_len, and
+ * ac_error_count_samples over images this context uploaded.  Any other call made
+ * with E != 2 -- ragged windows, a call mixing ragged and equal jobs, windows over
+ * 256 bases, k <= 15, k = 17, packed images with window descriptors
+ * (ac_error_count, ac_error_count_images, ac_count), AC_BITSLICE=0 -- returns
+ * AC_ERR_INVALID before anything is launched; ac_last_error names the constraint.
+ * Nothing falls back: no count is ever produced under another budget than the
+ * one set.
+ *
+ * ac_set_max_errors: e > 3 or a NULL ctx returns AC_ERR_INVALID (the budget is
+ * unchanged).  ac_max_errors: the context's budget (2 for a NULL ctx).
+ */
+ac_status ac_set_max_errors(ac_ctx* ctx, uint32_t e);
+uint32_t ac_max_errors(const ac_ctx* ctx);
+
 #ifdef __cplusplus
 }
 #endif
