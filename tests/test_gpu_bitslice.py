@@ -20,7 +20,8 @@ from tests import cases
 pytestmark = pytest.mark.gpu
 K = 16
 # the kernel a qualifying launch must report: the bit-sliced one, unless the run keeps every launch on
-# the word-parallel kernel (AC_BITSLICE=0: the whole suite is also run that way)
+# the word-parallel kernel (AC_BITSLICE=0: a run done by hand, which no default run makes -- the default
+# run's tests of that kernel's equal-window code are tests/test_gpu_word_parallel.py)
 WORD, BITSLICE = 0, (0 if os.environ.get("AC_BITSLICE", "1") == "0" else 1)
 AC_TESTING_ALL_AHEAD, AC_TESTING_DEVICE_PACK = 2, 8
 

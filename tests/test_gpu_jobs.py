@@ -136,7 +136,10 @@ def test_inline_n_records(counter, L):
     at L = 100/101, 2 at 150, 1 at 151, none at 128 (no room: the N bitmap path), 4 at 16 / 40.
     Windows with 0..6 N bases -- records that hold them all and records that overflow (their
     N-bitmap words are used) -- with N on word edges (0, 15, 16, 31, 32, 63, 64, L - 1), in
-    one job beside an N-free job and a job whose only N-holders overflow."""
+    one job beside an N-free job and a job whose only N-holders overflow.
+    At k = 16 every case here reaches the bit-sliced kernel (bs_count.inc) in a default run, and the
+    word-parallel kernel only under AC_BITSLICE=0; the same jobs at that kernel's own k (8, 10, 15, 17),
+    and at k = 16 / 22 in a child with AC_BITSLICE=0, are tests/test_gpu_word_parallel.py's."""
     ws = _n_record_windows(L, 3000, L, [0, 1, 0, 2, 0, 3, 4, 0, 5, 6, 1], spots=(0, 15, 16, 31, 32, 63, 64, L - 1))
     over = _n_record_windows(L + 1, 900, L, [0, 0, 7])
     clean = _n_record_windows(L + 2, 700, L, [0])
