@@ -144,6 +144,16 @@ def load():
         L.ac_set_max_errors.restype = ctypes.c_int
         L.ac_max_errors.argtypes = [vp]
         L.ac_max_errors.restype = ctypes.c_uint32
+    if hasattr(L, "ac_window_hits_words"):  # (an A/B build of an older library lacks the hit levels)
+        pp32 = ctypes.POINTER(p32)
+        L.ac_window_hits_words.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]
+        L.ac_window_hits_words.restype = ctypes.c_uint64
+        L.ac_window_hits_device.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ACSegment), ctypes.c_uint32, p32, pp32, vp]
+        L.ac_window_hits_device.restype = ctypes.c_int
+        L.ac_window_hits_samples.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ACSampleJob), ctypes.c_uint32, pp32]
+        L.ac_window_hits_samples.restype = ctypes.c_int
+        L.ac_hit_level_counts_device.argtypes = [vp, p32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, p32, vp]
+        L.ac_hit_level_counts_device.restype = ctypes.c_int
     L.ac_exact_path.argtypes = [vp]
     L.ac_exact_path.restype = ctypes.c_int
     pint = ctypes.POINTER(ctypes.c_int)

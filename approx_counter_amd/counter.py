@@ -108,6 +108,60 @@ def pack_windows(windows) -> PackedSample:
     return PackedSample(codes, nmask, out_start[: len(arrs)], out_len[: len(arrs)], n_bases)
 
 
+def hits_words(n_kmers: int, n_windows: int, max_errors: int = 2) -> int:
+    """ac_window_hits_words: the u32 words of one segment's hit matrix, (E + 1) x n_windows x ceil(n_kmers / 32)."""
+    return (int(max_errors) + 1) * int(n_windows) * ((int(n_kmers) + 31) // 32)
+
+
+def unpack_hits(levels, n_kmers: int) -> np.ndarray:
+    """A hit matrix's bits: `levels` is (E + 1, n_windows, words) uint32, bit c % 32 of word c // 32 =
+    candidate c; returns bool (E + 1, n_windows, n_kmers).  Pure numpy."""
+    lv = np.ascontiguousarray(levels, dtype="<u4")
+    if lv.ndim != 3 or lv.shape[2] != (int(n_kmers) + 31) // 32:
+        raise ValueError("hit matrix must be (levels, n_windows, ceil(n_kmers / 32))")
+    bits = np.unpackbits(lv.view(np.uint8).reshape(lv.shape[0], lv.shape[1], lv.shape[2] * 4), axis=-1,
+                         bitorder="little")
+    return bits[:, :, : int(n_kmers)].astype(bool)
+
+
+def distances_from_hits(hit) -> np.ndarray:
+    """uint8 (n_windows, n_kmers) distances from nested levels (`hit`: bool (E + 1, n_windows, n_kmers),
+    hit[e] = within e edits): the first level that holds the pair, E + 1 meaning "more than E".  Levels
+    that do not nest (a pair at level e missing from level e + 1) raise ValueError."""
+    hit = np.asarray(hit, dtype=bool)
+    if hit.ndim != 3:
+        raise ValueError("hit must be (levels, n_windows, n_kmers)")
+    if (hit[:-1] & ~hit[1:]).any():
+        raise ValueError("hit levels do not nest")
+    return (hit.shape[0] - hit.sum(axis=0)).astype(np.uint8)
+
+
+class WindowHits:
+    """One part's counts and hit levels (ac_window_hits_samples): which windows hold each k-mer within
+    0..E edits -- the reference's tcount[errors][read] (approx_counter.cpp:553-565) before it is summed."""
+
+    def __init__(self, counts, levels, n_kmers: int):
+        self.counts = counts
+        self.levels = np.asarray(levels, dtype=np.uint32)  # (E + 1, n_windows, words)
+        self.n_kmers = int(n_kmers)
+
+    @property
+    def max_errors(self) -> int:
+        return int(self.levels.shape[0]) - 1
+
+    def hit(self, e: int) -> np.ndarray:
+        """bool (n_windows, n_kmers): window w holds k-mer c within e edits."""
+        return unpack_hits(self.levels[e:e + 1], self.n_kmers)[0]
+
+    def distances(self) -> np.ndarray:
+        """uint8 (n_windows, n_kmers): min(d, E + 1)."""
+        return distances_from_hits(unpack_hits(self.levels, self.n_kmers))
+
+    def level_counts(self) -> np.ndarray:
+        """uint64 (E + 1, n_kmers): the windows within e edits of every k-mer; their sum over e is .counts."""
+        return unpack_hits(self.levels, self.n_kmers).sum(axis=1, dtype=np.uint64)
+
+
 class _PinnedBlock:
     """One ac_host_alloc block, released when the last array viewing it goes (numpy keeps this
     object as the arrays' base)."""
@@ -345,6 +399,42 @@ class ApproxCounter:
         """ac_error_count_samples: [(kmers, device sample from upload_sample), ...], one fused launch."""
         return self._sample_jobs(self._L.ac_error_count_samples, k, parts)
 
+    def window_hits(self, k: int, parts) -> list:
+        """ac_window_hits_samples: [(kmers, PackedSample), ...] (up to 4 parts, e.g. both read ends) are
+        uploaded into the context's sample slots and counted in one fused launch that also writes every
+        window's hit levels; returns one WindowHits per part.  Only where the bit-sliced kernel counts
+        (k = 16 or 18..32, equal windows of 1..256 bases, a single-device context), at the context's
+        edit budget; anything else raises (AC_ERR_INVALID)."""
+        if not hasattr(self._L, "ac_window_hits_samples"):
+            raise _lib.ApproxCounterError(_lib.AC_ERR_INVALID, "this build of the library has no ac_window_hits_samples")
+        E = self.max_errors
+        keep, arr, mats = [], [], []
+        for slot, (km, smp) in enumerate(parts):
+            km = np.ascontiguousarray(np.asarray(km, dtype=np.uint64))
+            c = np.zeros(max(km.size, 1), dtype=np.uint64)
+            # (all ones: the call writes every word, so one it missed would show as a row of hits, not pass as none)
+            m = np.full(max(hits_words(km.size, smp.n_windows, E), 1), 0xFFFFFFFF, dtype=np.uint32)
+            keep.append((km, c, smp.n_windows))
+            mats.append(m)
+            arr.append(ACSampleJob(_ptr(km if km.size else np.zeros(1, np.uint64), ctypes.c_uint64), int(km.size),
+                                   self.upload_sample(smp, slot), _ptr(c, ctypes.c_uint64)))
+        a = (ACSampleJob * len(arr))(*arr)
+        hp = (_lib.p32 * len(arr))(*[_ptr(m, ctypes.c_uint32) for m in mats])
+        check(self._L.ac_window_hits_samples(self._h, int(k), a, len(arr), hp), self._h)
+        return [WindowHits(c[: km.size], m[: hits_words(km.size, nw, E)].reshape(E + 1, nw, (km.size + 31) // 32), km.size)
+                for (km, c, nw), m in zip(keep, mats)]
+
+    def hit_level_counts(self, hits, n_kmers: int, n_windows: int, levels: int, stream=None):
+        """ac_hit_level_counts_device over a device hit matrix (a torch tensor of `levels` planes): returns
+        an int32 device tensor (levels, n_kmers), the windows within e edits of every k-mer (asynchronous)."""
+        import torch
+
+        out = torch.empty((int(levels), max(int(n_kmers), 1)), dtype=torch.int32, device=hits.device)
+        p = lambda t: ctypes.cast(ctypes.c_void_p(t.data_ptr()), _lib.p32)  # noqa: E731
+        check(self._L.ac_hit_level_counts_device(self._h, p(hits), int(n_kmers), int(n_windows), int(levels), p(out),
+                                                 ctypes.c_void_p(stream or 0)), self._h)
+        return out[:, : int(n_kmers)]
+
     def exact_path(self) -> int:
         """ac_exact_path: 1 partitioned, 0 hash table, -1 no exact count yet."""
         return int(self._L.ac_exact_path(self._h))
@@ -405,11 +495,14 @@ class ApproxCounter:
         count_device (saves the per-call ctypes marshalling in launch loops)."""
         return (ACSegment * len(segments))(*[s.as_struct() for s in segments])
 
-    def count_device(self, k: int, segments, stream=None, accumulate: bool = False, window_len=None) -> None:
+    def count_device(self, k: int, segments, stream=None, accumulate: bool = False, window_len=None, hits=None) -> None:
         """ac_error_count_device over DeviceSegment objects, or an array from
         segment_array (asynchronous).  window_len (one per segment): the samples'
         windows all have that length and sit back to back at ceil32 strides
-        (start / length are not read).  accumulate: AC_DEVICE_ACCUMULATE."""
+        (start / length are not read).  accumulate: AC_DEVICE_ACCUMULATE.
+        hits (one device tensor per segment, hits_words(...) int32 / uint32 words each; None for a segment
+        without work): ac_window_hits_device -- the same launch also writes the windows' hit levels
+        (window_len required, no accumulate)."""
         arr = segments if isinstance(segments, ctypes.Array) else self.segment_array(segments)
         wp = None
         if window_len is not None:
@@ -417,8 +510,17 @@ class ApproxCounter:
             if wl.size != len(arr):
                 raise ValueError("one window_len per segment")
             wp = _ptr(wl, ctypes.c_uint32)
-        st = self._L.ac_error_count_device(self._h, int(k), arr, len(arr), wp, 1 if accumulate else 0,
-                                           ctypes.c_void_p(stream or 0))
+        if hits is not None:
+            if accumulate:
+                raise _lib.ApproxCounterError(_lib.AC_ERR_INVALID, "window hits: accumulate mode is refused")
+            if len(hits) != len(arr):
+                raise ValueError("one hits tensor per segment")
+            hp = (_lib.p32 * len(arr))(*[ctypes.cast(ctypes.c_void_p(h.data_ptr() if h is not None else 0), _lib.p32)
+                                         for h in hits])
+            st = self._L.ac_window_hits_device(self._h, int(k), arr, len(arr), wp, hp, ctypes.c_void_p(stream or 0))
+        else:
+            st = self._L.ac_error_count_device(self._h, int(k), arr, len(arr), wp, 1 if accumulate else 0,
+                                               ctypes.c_void_p(stream or 0))
         if st:
             check(st, self._h)
 

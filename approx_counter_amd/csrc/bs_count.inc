@@ -1,5 +1,6 @@
 // bs_count.inc -- the bit-sliced count kernel's body (DESIGN.md §4e), included by wm_count.hip (three NFA
-// rows: edit budgets 0..2) and by bs3_count.hip (four rows: budget 3) inside their anonymous namespaces:
+// rows: edit budgets 0..2), by bs3_count.hip (four rows: budget 3) and by bsh_count.hip (either, and the
+// windows' hit words stored beside the counts) inside their anonymous namespaces:
 // the NFA's place in the frame of count_frame.inc (deal, staged prologue,
 // sub-queues, gate, count hand-off -- the word-parallel kernel's), with another mapping of a wave
 // onto the work.
@@ -112,9 +113,13 @@ struct BsNfa<K, 3> {
 
 // R = 3: the edit budget E = a.max_errors is 0, 1 or 2 (a smaller budget drops levels where a row's
 // hit masks become counts); R = 4: E = 3.
-template <int K, bool STAGED, int R = 3>
+// HITS (bsh_count.hip, plain launches; DESIGN.md §4e "Hit levels"): where a row's masks become counts,
+// every lane whose window and candidate block exist also stores its hit word of each level 0..E to the
+// segment's matrix a.hits[si] -- one word, one lane, one row: no memset, no atomic.
+template <int K, bool STAGED, int R = 3, bool HITS = false>
 __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
     static_assert(K >= 3 && K <= 32, "a k-mer is one 64-bit word (dna2int layout: K = 32 fills it)");
+    static_assert(!(HITS && STAGED), "the staged instantiations do not write hits");
     constexpr uint32_t CS = BsLds<K>::CHAR_STRIDE;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -388,6 +393,27 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
         if (STAGED && !stage_ok) {  // the segment is skipped (the error word says so)
             item = n_items;
             break;
+        }
+        if constexpr (HITS) {
+            // Level e's word: bit j set iff candidate 32 (8 g + blk) + j lies within e edits of this
+            // window; bits of candidates past n_kmers are 0, and a window the kernel skipped (`has`
+            // false: live = 0) stores zeros.  A block past the group's last one has no word.
+            const uint32_t nblk = (ng + 31u) >> 5;
+            if (my_off != NO_WINDOW && blk < nblk) {
+                const uint32_t left = ng - 32u * blk;  // (>= 1) candidates of this block
+                const uint32_t keep = live & (left >= 32u ? ~0u : (1u << left) - 1u);
+                const uint64_t words = (uint64_t)((sg.n_kmers + 31u) >> 5);
+                uint32_t* hp = a.hits[si] + (uint64_t)(row * wpr + wl) * words + (BS_GROUP / 32u) * g + blk;
+                const uint64_t plane = (uint64_t)seg_nw * words;
+                if constexpr (R == 3) {
+                    hp[0] = ~s.a0 & keep;
+                    if (budget >= 1u) hp[plane] = ~s.a1 & keep;
+                    if (budget >= 2u) hp[2u * plane] = ~s.a2 & keep;
+                } else {
+#pragma unroll
+                    for (int e = 0; e < R; ++e) hp[(uint64_t)e * plane] = ~s.a[e] & keep;
+                }
+            }
         }
         if constexpr (R == 3) {
             bs::vc_add_e(vc, budget, s.a0, s.a1, s.a2, live);

@@ -286,6 +286,7 @@ void ac_destroy(ac_ctx* ctx) {
     for (void* p : ctx->d_buf)
         if (p) (void)hipFree(p);
     if (ctx->d_stage) (void)hipFree(ctx->d_stage);
+    if (ctx->d_hits) (void)hipFree(ctx->d_hits);
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
     for (auto& sc : ctx->sc) {
         if (sc.queue) (void)hipFree(sc.queue);
@@ -548,7 +549,9 @@ ac_status ac_count(ac_ctx* ctx, uint32_t k, const uint64_t* kmers, uint32_t n_km
 }
 
 
-ac_status ac_error_count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, uint32_t n_jobs) {
+// ac_error_count_samples, and -- hits_host: one host matrix per job -- ac_window_hits_samples.
+static ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, uint32_t n_jobs,
+                               uint32_t* const* hits_host) {
     if (!ctx) return fail(nullptr, AC_ERR_INVALID, "ctx is NULL");
     if (ac_status st = check_k(ctx, k)) return st;
     if (n_jobs > AC_MAX_JOBS) return fail(ctx, AC_ERR_INVALID, "too many jobs in one call (max 4)");
@@ -560,24 +563,6 @@ ac_status ac_error_count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* j
         total += jobs[j].n_kmers;
     }
     if (total == 0) return AC_OK;
-    AC_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    // every job's k-mers in one upload (d_buf[0]); uint32 counts in d_buf[5], one D2H
-    std::vector<uint64_t> km;
-    km.reserve(total);
-    for (uint32_t j = 0; j < n_jobs; ++j) km.insert(km.end(), jobs[j].kmers, jobs[j].kmers + jobs[j].n_kmers);
-    if (ac_status s2 = ensure(ctx, 0, sizeof(uint64_t) * total)) return s2;
-    if (ac_status s2 = ensure(ctx, 5, sizeof(uint32_t) * total)) return s2;
-    AC_HIP(ctx, hipMemcpyAsync(ctx->d_buf[0], km.data(), sizeof(uint64_t) * total, hipMemcpyHostToDevice, st));
-    ac_segment seg[AC_MAX_JOBS];
-    uint64_t base = 0;
-    for (uint32_t j = 0; j < n_jobs; ++j) {
-        seg[j].kmers = (const uint64_t*)ctx->d_buf[0] + base;
-        seg[j].n_kmers = jobs[j].n_kmers;
-        seg[j].sample = jobs[j].sample;
-        seg[j].counts = (uint32_t*)ctx->d_buf[5] + base;
-        base += jobs[j].n_kmers;
-    }
     // images this context uploaded: their equal-window / N-free findings (others: the general form)
     uint32_t ulen[AC_MAX_JOBS];
     bool no_n[AC_MAX_JOBS];
@@ -600,9 +585,57 @@ ac_status ac_error_count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* j
             (uint64_t)jobs[j].sample.n_windows * (((uint64_t)ulen[j] + 31u) & ~31ull) > jobs[j].sample.n_bases)
             ulen[j] = AC_NO_ULEN;
     }
-    if (ac_status rc = launch(ctx, k, seg, n_jobs, st, true, nullptr, 0, 0, no_n, ulen)) return rc;
+    // hits: refused here, before the k-mers' copy is enqueued (the launch asks again); then the jobs'
+    // device matrices, back to back in one block
+    uint32_t* d_hits[AC_MAX_JOBS] = {};
+    size_t hits_bytes[AC_MAX_JOBS] = {};
+    if (hits_host) {
+        bool live[AC_MAX_JOBS];
+        for (uint32_t j = 0; j < n_jobs; ++j) live[j] = jobs[j].n_kmers && jobs[j].sample.n_windows;
+        if (const char* why = acamd::hits_refusal(ctx->max_errors, k, n_jobs, live, ulen, !ctx->peers.empty()))
+            return fail(ctx, AC_ERR_INVALID, why);
+        size_t all = 0;
+        for (uint32_t j = 0; j < n_jobs; ++j) {
+            hits_bytes[j] = sizeof(uint32_t) *
+                            (size_t)ac_window_hits_words(jobs[j].n_kmers, jobs[j].sample.n_windows, ctx->max_errors);
+            if (live[j] && !hits_host[j]) return fail(ctx, AC_ERR_INVALID, "window hits: hits_host[j] is NULL for a job with work");
+            all += align256(hits_bytes[j]);
+        }
+        AC_HIP(ctx, hipSetDevice(ctx->device));
+        if (ac_status s2 = grow(ctx, &ctx->d_hits, &ctx->d_hits_cap, all)) return s2;
+        size_t at = 0;
+        for (uint32_t j = 0; j < n_jobs; ++j) {
+            d_hits[j] = (uint32_t*)((char*)ctx->d_hits + at);
+            at += align256(hits_bytes[j]);
+        }
+    }
+    AC_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    // every job's k-mers in one upload (d_buf[0]); uint32 counts in d_buf[5], one D2H
+    std::vector<uint64_t> km;
+    km.reserve(total);
+    for (uint32_t j = 0; j < n_jobs; ++j) km.insert(km.end(), jobs[j].kmers, jobs[j].kmers + jobs[j].n_kmers);
+    if (ac_status s2 = ensure(ctx, 0, sizeof(uint64_t) * total)) return s2;
+    if (ac_status s2 = ensure(ctx, 5, sizeof(uint32_t) * total)) return s2;
+    AC_HIP(ctx, hipMemcpyAsync(ctx->d_buf[0], km.data(), sizeof(uint64_t) * total, hipMemcpyHostToDevice, st));
+    ac_segment seg[AC_MAX_JOBS];
+    uint64_t base = 0;
+    for (uint32_t j = 0; j < n_jobs; ++j) {
+        seg[j].kmers = (const uint64_t*)ctx->d_buf[0] + base;
+        seg[j].n_kmers = jobs[j].n_kmers;
+        seg[j].sample = jobs[j].sample;
+        seg[j].counts = (uint32_t*)ctx->d_buf[5] + base;
+        base += jobs[j].n_kmers;
+    }
+    if (ac_status rc = launch(ctx, k, seg, n_jobs, st, true, nullptr, 0, 0, no_n, ulen, nullptr, nullptr,
+                              hits_host ? d_hits : nullptr))
+        return rc;
     ctx->h_counts.resize(total);
     AC_HIP(ctx, hipMemcpyAsync(ctx->h_counts.data(), ctx->d_buf[5], sizeof(uint32_t) * total, hipMemcpyDeviceToHost, st));
+    if (hits_host)
+        for (uint32_t j = 0; j < n_jobs; ++j)
+            if (jobs[j].n_kmers && jobs[j].sample.n_windows)
+                AC_HIP(ctx, hipMemcpyAsync(hits_host[j], d_hits[j], hits_bytes[j], hipMemcpyDeviceToHost, st));
     if (ac_status rc = ac_check(ctx, st)) return rc;  // synchronises the stream
     base = 0;
     for (uint32_t j = 0; j < n_jobs; ++j)
@@ -610,6 +643,49 @@ ac_status ac_error_count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* j
     return AC_OK;
 }
 
+ac_status ac_error_count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, uint32_t n_jobs) {
+    return count_samples(ctx, k, jobs, n_jobs, nullptr);
+}
+
+uint64_t ac_window_hits_words(uint32_t n_kmers, uint32_t n_windows, uint32_t max_errors) {
+    return (uint64_t)(max_errors + 1u) * n_windows * (((uint64_t)n_kmers + 31u) / 32u);
+}
+
+ac_status ac_window_hits_device(ac_ctx* ctx, uint32_t k, const ac_segment* segments, uint32_t n_segments,
+                                const uint32_t* window_len, uint32_t* const* hits, void* hip_stream) {
+    if (!ctx) return fail(nullptr, AC_ERR_INVALID, "ctx is NULL");
+    if (n_segments > AC_MAX_SEGS) return fail(ctx, AC_ERR_INVALID, "too many segments in one launch (max 4)");
+    if (n_segments && !hits) return fail(ctx, AC_ERR_INVALID, "window hits: hits is NULL");
+    uint32_t ul[AC_MAX_SEGS];
+    if (window_len)
+        for (uint32_t i = 0; i < n_segments; ++i) {
+            if (window_len[i] == AC_NO_ULEN) return fail(ctx, AC_ERR_INVALID, "window_len out of range");
+            ul[i] = window_len[i];
+        }
+    static uint32_t* const none[AC_MAX_SEGS] = {};
+    AC_HIP(ctx, hipSetDevice(ctx->device));
+    return launch(ctx, k, segments, n_segments, (hipStream_t)hip_stream, true, nullptr, 0, 0, nullptr,
+                  window_len ? ul : nullptr, nullptr, nullptr, hits ? hits : none);
+}
+
+ac_status ac_window_hits_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, uint32_t n_jobs,
+                                 uint32_t* const* hits_host) {
+    if (!ctx) return fail(nullptr, AC_ERR_INVALID, "ctx is NULL");
+    if (n_jobs && !hits_host) return fail(ctx, AC_ERR_INVALID, "window hits: hits_host is NULL");
+    static uint32_t* const none[AC_MAX_JOBS] = {};
+    return count_samples(ctx, k, jobs, n_jobs, hits_host ? hits_host : none);
+}
+
+ac_status ac_hit_level_counts_device(ac_ctx* ctx, const uint32_t* hits, uint32_t n_kmers, uint32_t n_windows,
+                                     uint32_t levels, uint32_t* level_counts, void* hip_stream) {
+    if (!ctx) return fail(nullptr, AC_ERR_INVALID, "ctx is NULL");
+    if (levels < 1u || levels > 4u) return fail(ctx, AC_ERR_INVALID, "hit levels: levels must be 1..4");
+    if (n_kmers && !level_counts) return fail(ctx, AC_ERR_INVALID, "hit levels: level_counts is NULL");
+    if (n_kmers && n_windows && !hits) return fail(ctx, AC_ERR_INVALID, "hit levels: hits is NULL");
+    AC_HIP(ctx, hipSetDevice(ctx->device));
+    AC_HIP(ctx, acamd::launch_hit_level_counts(hits, n_kmers, n_windows, levels, level_counts, (hipStream_t)hip_stream));
+    return AC_OK;
+}
 
 ac_status ac_set_max_errors(ac_ctx* ctx, uint32_t e) {
     if (!ctx) return fail(nullptr, AC_ERR_INVALID, "ctx is NULL");

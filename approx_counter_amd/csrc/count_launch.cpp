@@ -51,9 +51,11 @@ void ensure_warm(ac_ctx* ctx) {
 // That was measured at four waves per SIMD and holds for the kernels of that residency (k = 16) only:
 // the wider patterns' kernels, at 2-3 waves per SIMD, launch every resident workgroup.
 // AC_BS_WAVES_PCT (1..100) sets the share for every bit-sliced launch instead, for A/B runs.
-static uint64_t bs_launch_waves(uint32_t k, uint32_t max_errors, uint64_t items, uint64_t resident) {
+static uint64_t bs_launch_waves(uint32_t k, uint32_t max_errors, bool hits, uint64_t items, uint64_t resident) {
     static const int pct = env_int("AC_BS_WAVES_PCT", 0);
-    const bool three_of_four = acamd::bs_waves_per_simd((int)k, max_errors == 3u ? 3 : 2) == 4 && items > resident &&
+    const int e = max_errors == 3u ? 3 : 2;
+    const int per_simd = hits ? acamd::bsh_waves_per_simd((int)k, e) : acamd::bs_waves_per_simd((int)k, e);
+    const bool three_of_four = per_simd == 4 && items > resident &&
                                4 * items <= 5 * resident;
     const uint64_t want = pct > 0 ? resident * (uint64_t)std::min(pct, 100) / 100
                                   : three_of_four ? resident * 3 / 4 : resident;
@@ -72,9 +74,12 @@ static uint64_t bs_launch_waves(uint32_t k, uint32_t max_errors, uint64_t items,
 // Staged launch (the early-launch stage): the kernel copies each
 // segment's region from src (the pinned block) to dst once the host flags it in
 // host_hdr, and reports its completion there.
+// `hits` (optional; plain launches that store their counts): per segment the device matrix the launch
+// also writes its windows' hit words to (DESIGN.md §4e "Hit levels"); refused -- hits_refusal -- unless
+// the launch is bit-sliced.
 ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hipStream_t stream, bool zero,
                  uint32_t* err, int scratch, uint32_t wave_div, const bool* no_n, const uint32_t* ulen,
-                 const StageLaunch* stage, const bool* nrec) {
+                 const StageLaunch* stage, const bool* nrec, uint32_t* const* hits) {
     ensure_warm(ctx);
     ac_ctx::Scratch& sc = ctx->sc[scratch];
     if (ac_status st = check_k(ctx, k)) return st;
@@ -97,6 +102,19 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
     // The context's edit budget (ac_set_max_errors): another one than 2 counts on a bit-sliced launch
     // or not at all -- refused here, before anything is enqueued.
     const uint32_t E = ctx->max_errors;
+    // (hits first: its refusal names the hits call's own constraint)
+    if (hits) {
+        if (const char* why = acamd::hits_refusal(E, k, n, live, ulen, !ctx->peers.empty()))
+            return fail(ctx, AC_ERR_INVALID, why);
+        if (staged || !zero) return fail(ctx, AC_ERR_INVALID, "window hits need a plain launch that stores its counts");
+        for (uint32_t i = 0; i < n; ++i)
+            if (live[i] && !hits[i]) return fail(ctx, AC_ERR_INVALID, "window hits: hits[i] is NULL for a segment with work");
+        for (uint32_t i = 0; i < n; ++i)
+            for (uint32_t j = i + 1; j < n; ++j)
+                if (live[i] && live[j] && segs[i].counts < segs[j].counts + segs[j].n_kmers &&
+                    segs[j].counts < segs[i].counts + segs[i].n_kmers)
+                    return fail(ctx, AC_ERR_INVALID, "window hits: segments' count vectors overlap");
+    }
     if (const char* why = acamd::budget_refusal(E, k, n, live, ulen)) return fail(ctx, AC_ERR_INVALID, why);
     const uint32_t cpw = acamd::launch_group_size(k, staged, bs);
     uint64_t items = 0;
@@ -132,14 +150,16 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
     // to its windows, so every sub-queue holds about the same work.  Workgroups
     // of AC_WAVES_PER_BLOCK waves are dealt round-robin over blocks of that many
     // consecutive sub-queues (one candidate group each).
-    uint32_t& res_p = !bs ? ctx->resident[staged][P] : E == 3u ? ctx->resident_bs3[staged][k] : ctx->resident_bs[staged][k];
+    uint32_t& res_p = !bs    ? ctx->resident[staged][P]
+                      : hits ? ctx->resident_bsh[E == 3u][k]
+                             : E == 3u ? ctx->resident_bs3[staged][k] : ctx->resident_bs[staged][k];
     if (!res_p)
-        AC_HIP(ctx, bs ? acamd::resident_waves_bs(k, staged, ctx->cu_count, &res_p, E == 3u ? 3u : 2u)
+        AC_HIP(ctx, bs ? acamd::resident_waves_bs(k, staged, ctx->cu_count, &res_p, E == 3u ? 3u : 2u, hits != nullptr)
                        : acamd::resident_waves(P, staged, ctx->cu_count, &res_p));
     const uint64_t fit = wave_div > 1 ? std::max<uint64_t>(AC_WAVES_PER_BLOCK, res_p / wave_div / AC_WAVES_PER_BLOCK *
                                                                                    AC_WAVES_PER_BLOCK)
                                       : res_p;
-    const uint64_t resident = bs ? bs_launch_waves(k, E, items, fit) : fit;
+    const uint64_t resident = bs ? bs_launch_waves(k, E, hits != nullptr, items, fit) : fit;
     const uint32_t wpw = (uint32_t)std::max<uint64_t>(1, (items + resident - 1) / resident);
 #ifdef AC_FORCE_CHUNK  // A/B builds (tools/variants.sh): fixed item size
     const uint32_t chunk = AC_FORCE_CHUNK;
@@ -287,6 +307,10 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
     // last live segment whose queue_begin <= its sub-queue.
     a.bs = bs ? 1u : 0u;
     a.max_errors = E;
+    if (hits) {
+        a.want_hits = 1u;
+        for (uint32_t i = 0; i < n; ++i) a.hits[i] = a.seg[i].queue_begin != ~0u ? hits[i] : nullptr;
+    }
     a.total_waves = wave;
     if (wave) ctx->last_kernel = bs ? 1 : 0;
     ctx->last_waves = wave;

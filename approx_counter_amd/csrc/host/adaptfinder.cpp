@@ -11,6 +11,9 @@
 //   --seed N        seed the read sampling (the reference always uses std::random_device)
 //   --max-errors E  edit budget of the approximate count, 0..3 (the reference hard-codes 2, the default):
 //                   a window adds max(0, E + 1 - d) to a k-mer's count (ac_set_max_errors)
+//   --levels        beside every <out>_<run>.<end> file a <out>_<run>.<end>.levels file: per k-mer, in the
+//                   same order, the sampled windows that hold it within 0, 1, .. E edits (the reference's
+//                   per-level bitfields, approx_counter.cpp:553-565, before their sum; ac_window_hits_samples)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -23,6 +26,7 @@
 #include <string>
 #include <vector>
 
+#include "../hit_levels.h"
 #include "approx_counter_amd.h"
 #include "host_stages.h"
 
@@ -76,6 +80,11 @@ const Opt OPTS[] = {
      "[MI355X build] edit budget E of the approximate count, 0 to 3: a window adds max(0, E + 1 - distance); "
      "default 2, the reference's. Another value needs a kmer size of 16 or 18 to 32, a sampling length up to 255 "
      "and one GPU."},
+    {"", "levels", Kind::Flag,
+     "[MI355X build] also write <out>_<run>.<end>.levels: one line per k-mer of the main file, in its order, the "
+     "k-mer and the number of sampled windows holding it within 0, 1, .. max-errors edits (they sum to its count). "
+     "Needs a kmer size of 16 or 18 to 32, a sampling length up to 255, one GPU and reads of at least the sampling "
+     "length."},
     {"", "host-exact", Kind::Flag,
      "[MI355X build] the reference's host stages: whole reads in memory, exact k-mer count on the CPU"},
     {"", "dump-sample", Kind::String,
@@ -221,6 +230,34 @@ bool write_image(const PackedImage& p, const std::string& path) {
     return std::fclose(f) == 0 && ok;
 }
 
+// --levels: `ranked` is the main file's content; one line per k-mer of it, the k-mer and its `levels` level
+// counts -- column sums of the job's hit matrix (hits: levels x n_windows x ceil(n / 32) words, candidate c =
+// kmers[c]), by the column counter the library's level-count kernel runs (hit_levels.h).
+bool export_levels(const pair_vector& ranked, const std::vector<uint64_t>& kmers, const std::vector<uint32_t>& hits,
+                   uint32_t n_windows, uint32_t levels, uint32_t k, const std::string& path) {
+    const uint32_t n = (uint32_t)kmers.size(), words = (n + 31u) / 32u;
+    std::vector<uint32_t> lc((size_t)levels * n, 0u);
+    for (uint32_t e = 0; e < levels; ++e)
+        for (uint32_t col = 0; col < words; ++col) {
+            uint32_t cnt[32] = {};
+            acamd::bs::hc_column(hits.data() + (size_t)e * n_windows * words, words, col, 0u, n_windows, 1u, cnt);
+            for (uint32_t j = 0; j < 32u && 32u * col + j < n; ++j) lc[(size_t)e * n + 32u * col + j] = cnt[j];
+        }
+    std::map<uint64_t, uint32_t> index;  // (the exact count's k-mers are distinct)
+    for (uint32_t c = 0; c < n; ++c) index.emplace(kmers[c], c);
+    std::FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) return false;
+    std::string line;
+    for (const auto& kv : ranked) {
+        const uint32_t c = index.at(kv.first);
+        line = int2dna(kv.first, k);
+        for (uint32_t e = 0; e < levels; ++e) line += '\t' + std::to_string(lc[(size_t)e * n + c]);
+        line += '\n';
+        std::fwrite(line.data(), 1, line.size(), f);
+    }
+    return std::fclose(f) == 0;
+}
+
 void open_devices(Devices& dev, uint64_t n_gpus, uint64_t max_errors) {
     if (dev.ctx) return;
     if (n_gpus < 1) n_gpus = 1;
@@ -308,6 +345,7 @@ int main(int argc, char const** argv) {
     get_option(args, "max-errors", max_errors);
     skip_end = skip_end || args.val.count("skip_end");
     const bool host_exact = args.val.count("host-exact") > 0;
+    const bool levels = args.val.count("levels") > 0;
     std::string dump_sample;
     get_option(args, "dump-sample", dump_sample);
     const std::string input_file = args.input;
@@ -339,6 +377,20 @@ int main(int argc, char const** argv) {
                           : n_gpus > 1     ? "--max-errors other than 2 needs one GPU (-g 1)"
                           : host_exact     ? "--max-errors other than 2 cannot be combined with --host-exact"
                                            : nullptr;
+        if (why) {
+            std::cerr << error_pref << why << std::endl;
+            return 1;
+        }
+    }
+    // --levels: the hit levels come from the same kernel family under the same constraints
+    // (ac_window_hits_samples); what only the sample can tell -- read ends of unequal length -- the
+    // library refuses when the count is asked for.
+    if (levels) {
+        const char* why = !(k == 16 || (k >= 18 && k <= 32)) ? "--levels needs a kmer size (-k) of 16 or 18 to 32"
+                          : sl > 255                         ? "--levels needs a sampling length (-sl) of at most 255"
+                          : n_gpus > 1                       ? "--levels needs one GPU (-g 1)"
+                          : host_exact                       ? "--levels cannot be combined with --host-exact"
+                                                             : nullptr;
         if (why) {
             std::cerr << error_pref << why << std::endl;
             return 1;
@@ -420,14 +472,24 @@ int main(int argc, char const** argv) {
                 ct[e].assign(km[e].size(), 0);
                 jobs[e] = ac_sample_job{km[e].data(), (uint32_t)km[e].size(), ac_windows{}, ct[e].data()};
             }
+            // --levels: the hits call in place of the plain count (the same launch yields the counts)
+            std::vector<std::vector<uint32_t>> hits(pending.size());
+            std::vector<uint32_t*> hits_p(pending.size());
             try {
                 devices();
                 const bool on_device = !host_exact && dev.shards == 1;  // the samples uploaded for the exact count
                 for (size_t e = 0; e < pending.size(); ++e)
                     jobs[e].sample = on_device ? pending[e].dsample : view(pending[e].img);
+                if (levels)
+                    for (size_t e = 0; e < pending.size(); ++e) {
+                        hits[e].assign((size_t)ac_window_hits_words(jobs[e].n_kmers, jobs[e].sample.n_windows,
+                                                                    (uint32_t)max_errors) + 1, 0u);
+                        hits_p[e] = hits[e].data();
+                    }
                 const ac_status st =
-                    on_device ? ac_error_count_samples(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size())
-                              : ac_error_count_images(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size());
+                    levels      ? ac_window_hits_samples(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size(), hits_p.data())
+                    : on_device ? ac_error_count_samples(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size())
+                                : ac_error_count_images(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size());
                 if (st != AC_OK) throw std::runtime_error(ac_last_error(dev.ctx));
             } catch (const std::exception& e) {
                 std::cerr << error_pref << "approximate count failed: " << e.what() << std::endl;
@@ -442,6 +504,12 @@ int main(int argc, char const** argv) {
                 if (!export_counter(sorted_error_count, (uint32_t)k, path)) {
                     std::cerr << error_pref + "Failed to export approximate k-mer count" << std::endl;
                     std::cerr << "Path: " << path << std::endl;
+                    return false;
+                }
+                if (levels && !export_levels(sorted_error_count, km[e], hits[e], jobs[e].sample.n_windows,
+                                             (uint32_t)max_errors + 1, (uint32_t)k, path + ".levels")) {
+                    std::cerr << error_pref + "Failed to export the hit levels" << std::endl;
+                    std::cerr << "Path: " << path + ".levels" << std::endl;
                     return false;
                 }
                 if (mr_v > 0) print("Done", tab_level);

@@ -40,6 +40,24 @@ const char* budget_refusal(uint32_t max_errors, uint32_t k, uint32_t n, const bo
     return "max_errors other than 2 needs the bit-sliced count kernel (AC_BITSLICE=0 turns it off)";
 }
 
+const char* hits_refusal(uint32_t max_errors, uint32_t k, uint32_t n, const bool* live, const uint32_t* ulen,
+                         bool multi_device) {
+    if (max_errors > 3u) return "max_errors must be 0..3";
+    if (multi_device) return "window hits need a single-device context (this one is an ac_create_multi context)";
+    if (!bs::has_k(k)) return "window hits need k = 16 or 18..32 (the bit-sliced count kernel's lengths)";
+    if (!ulen) return "window hits need equal windows of 1..256 bases (this launch has ragged windows)";
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!live[i]) continue;
+        if (ulen[i] == AC_NO_ULEN)
+            return "window hits need equal windows of 1..256 bases in every job of a launch "
+                   "(this launch has ragged windows)";
+        if (ulen[i] == 0u || ulen[i] > 256u)
+            return "window hits need equal windows of 1..256 bases (this launch's are longer)";
+    }
+    if (!bs_launch(k, n, live, ulen)) return "window hits need the bit-sliced count kernel (AC_BITSLICE=0 turns it off)";
+    return nullptr;
+}
+
 uint32_t launch_group_size(uint32_t k, bool staged, bool bs) {
     return bs ? BS_GROUP : cands_per_wave(pack_factor(k), staged);
 }

@@ -100,6 +100,12 @@ bool bs_launch(uint32_t k, uint32_t n, const bool* live, const uint32_t* ulen);
 // launch may run at `max_errors`, else the constraint it breaks, as the text of the caller's error --
 // nothing is launched then: no launch ever counts under another budget than the one asked for.
 const char* budget_refusal(uint32_t max_errors, uint32_t k, uint32_t n, const bool* live, const uint32_t* ulen);
+// The hit levels' question (ac_window_hits_*; DESIGN.md §4e "Hit levels"), asked of the same launch: the
+// hits-writing kernels are bit-sliced and plain, so a launch yields hits only where bs_launch routes it to
+// the bit-sliced kernel, on a single-device context, at the context's budget 0..3.  NULL when it may, else
+// the constraint it breaks -- nothing is launched then and nothing falls back.
+const char* hits_refusal(uint32_t max_errors, uint32_t k, uint32_t n, const bool* live, const uint32_t* ulen,
+                         bool multi_device);
 // Candidates of such a launch's candidate groups: BS_GROUP for a bit-sliced launch, else the
 // word-parallel kernel's candidates per wave.  Everything counted per group goes by it: the work
 // items, the acc slots, the sub-queues, a tagged launch's group error words and their polling.

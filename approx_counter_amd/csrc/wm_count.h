@@ -161,6 +161,11 @@ struct LaunchArgs {
     uint32_t bs;  // the bit-sliced kernel (bs_count.inc) counts this launch: `chunk` is in rows of windows
     uint32_t max_errors;  // the edit budget E (0..3) of the counts: a window adds max(0, E + 1 - d); other
                           // than 2 on bit-sliced launches only (3: the bs3_count.hip kernels)
+    // Hit levels (bsh_count.hip; DESIGN.md §4e "Hit levels"), appended so that no field above moves: per
+    // segment the device matrix the launch's hits kernel writes -- level e, window w, word c / 32 at
+    // hits[(e * n_windows + w) * ceil(n_kmers / 32) + c / 32] -- read by that kernel family only.
+    uint32_t* hits[AC_MAX_SEGS];
+    uint32_t want_hits;  // the launch runs a hits-writing kernel (plain bit-sliced launches only)
 };
 
 inline uint32_t pack_factor(uint32_t k) { return (32u / k) < AC_MAX_PACK ? (32u / k) : AC_MAX_PACK; }
@@ -202,6 +207,9 @@ constexpr int bs_waves_per_simd(int k, int max_errors = 2) {
     return max_errors == 3 ? (k <= BS3_K_MID ? 3 : 2)
                            : k <= 16 ? BS_WAVES_PER_SIMD : k <= BS_K_MID ? BS_WAVES_PER_SIMD_MID : 2;
 }
+// The hits-writing family (bsh_count.hip): the counting twin's residency for every K -- the stores sit
+// outside the 4-base block and the compiler's occupancy equals it (profiles/r12_bsh_codegen.txt).
+constexpr int bsh_waves_per_simd(int k, int max_errors = 2) { return bs_waves_per_simd(k, max_errors); }
 inline __host__ __device__ uint32_t bs_lane_shift(uint32_t n) {
     const uint32_t blocks = (n + 31u) / 32u;
     uint32_t s = 1;
@@ -214,9 +222,17 @@ inline uint64_t bs_rows(uint32_t n_kmers, uint32_t g, uint32_t cpw, uint32_t n_w
     const uint32_t wpr = 64u >> bs_lane_shift(n);
     return ((uint64_t)n_windows + wpr - 1u) / wpr;
 }
-hipError_t resident_waves_bs(uint32_t k, bool staged, int cu_count, uint32_t* waves, uint32_t max_errors = 2);
+hipError_t resident_waves_bs(uint32_t k, bool staged, int cu_count, uint32_t* waves, uint32_t max_errors = 2,
+                             bool hits = false);
 // bs3_count.hip: the E = 3 kernel for k (AC_BS_K_LIST), plain or staged; nullptr if there is none
 void (*bs3_kernel(uint32_t k, bool staged))(LaunchArgs);
+// bsh_count.hip: the plain hits-writing kernel for k (AC_BS_K_LIST) at edit budget max_errors (0..2: three
+// NFA rows, 3: four); nullptr if there is none
+void (*bsh_kernel(uint32_t k, uint32_t max_errors))(LaunchArgs);
+// bsh_count.hip: level_counts[e * n_kmers + c] = the windows of level plane e of a hit matrix that hold
+// candidate c (a column popcount); level_counts is zeroed on the stream first
+hipError_t launch_hit_level_counts(const uint32_t* hits, uint32_t n_kmers, uint32_t n_windows, uint32_t levels,
+                                   uint32_t* level_counts, hipStream_t stream);
 
 // Waves of the count kernel for pattern pack P that fit on the device at once.
 hipError_t resident_waves(uint32_t P, bool staged, int cu_count, uint32_t* waves);

@@ -445,6 +445,60 @@ ac_status ac_last_launch(const ac_ctx* ctx, uint64_t* waves, uint32_t* windows_p
 ac_status ac_set_max_errors(ac_ctx* ctx, uint32_t e);
 uint32_t ac_max_errors(const ac_ctx* ctx);
 
+/*
+ * Hit levels: which windows (reads) hold a k-mer within 0..E edits (additive
+ * exports of ABI 8).  The reference fills one bitfield per error level and read,
+ * tcount[errors][read] (approx_counter.cpp:553-565), and collapses them at once
+ * with vectorSum into the one count per k-mer (580-596); these calls hand out
+ * the bitfields themselves, as one dense bit matrix per level, beside the same
+ * counts.  With E = the context's edit budget (ac_set_max_errors), a segment of
+ * n_kmers candidates and n_windows windows has
+ *     words = ceil(n_kmers / 32)            u32 per window and level
+ *     hits[(e * n_windows + w) * words + c / 32], bit c % 32
+ *         set iff d(kmer c, window w) <= e,   e = 0..E
+ * (the levels nest: a bit set at level e is set at every level above it); bits
+ * of candidates >= n_kmers are 0, and a window the kernel skipped (reported by
+ * ac_check) holds zeros.  Every word of the matrix is written by the launch: the
+ * buffer needs no clearing.  count[c] = the number of set bits of candidate c
+ * over all levels and windows.
+ *   ac_window_hits_words   u32 words of one segment's matrix:
+ *                          (max_errors + 1) * n_windows * ceil(n_kmers / 32)
+ *   ac_window_hits_device  ac_error_count_device with window_len required, plus
+ *                          one device matrix per segment (hits[i], of
+ *                          ac_window_hits_words u32 at the context's budget);
+ *                          asynchronous on hip_stream, the counts stored to
+ *                          segments[i].counts by the same launch.  No flags:
+ *                          accumulate mode and count vectors that overlap are
+ *                          refused.
+ *   ac_window_hits_samples ac_error_count_samples (samples uploaded with
+ *                          ac_sample_upload_slot: the CLI's route) that also
+ *                          fills one host matrix per job (hits_host[j]);
+ *                          synchronous.
+ *   ac_hit_level_counts_device
+ *                          level_counts[e * n_kmers + c] = the windows of level
+ *                          plane e (e < levels, 1..4) that hold candidate c: a
+ *                          column popcount of a device matrix, asynchronous on
+ *                          hip_stream (level_counts, device memory, is zeroed
+ *                          first).  Their sum over e is the count of c.
+ * Where they run: only on launches the bit-sliced count kernel takes (k = 16 or
+ * 18..32, every segment with candidates and windows holding equal windows of
+ * 1..256 bases, AC_BITSLICE not 0), on single-device contexts, at any budget
+ * 0..3.  Everything else -- ragged windows (window_len NULL, or a sample this
+ * context did not upload as equal windows), a launch mixing ragged and equal
+ * jobs, windows over 256 bases, k <= 15, k = 17, AC_BITSLICE=0, an
+ * ac_create_multi context, a NULL matrix for a segment that has work -- returns
+ * AC_ERR_INVALID before anything is enqueued; ac_last_error names the
+ * constraint.  Nothing falls back, and the context stays usable.  The jobs stage
+ * (ac_error_count_jobs / _submit) does not produce hits.
+ */
+uint64_t ac_window_hits_words(uint32_t n_kmers, uint32_t n_windows, uint32_t max_errors);
+ac_status ac_window_hits_device(ac_ctx* ctx, uint32_t k, const ac_segment* segments, uint32_t n_segments,
+                                const uint32_t* window_len, uint32_t* const* hits, void* hip_stream);
+ac_status ac_window_hits_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, uint32_t n_jobs,
+                                 uint32_t* const* hits_host);
+ac_status ac_hit_level_counts_device(ac_ctx* ctx, const uint32_t* hits, uint32_t n_kmers, uint32_t n_windows,
+                                     uint32_t levels, uint32_t* level_counts, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

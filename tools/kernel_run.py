@@ -12,6 +12,10 @@ memory counters).  Same workload and launch as bench.py's kernel leg.
 from HIP events around them (back-to-back launches on resident input), for E = 3 against E = 2:
 
     python3 tools/kernel_run.py --config cfg5 --k 24 --max-errors 3 --warmup 20 --launches 100 --time
+
+--hits runs the hits-writing kernels (ac_window_hits_device: the same launch also stores every window's hit
+levels, DESIGN.md 4e "Hit levels") and prints the bytes of the matrices beside the time; --level-counts then
+times ac_hit_level_counts_device over the first segment's matrix and prints the rate its bytes were read at.
 """
 import argparse
 import os
@@ -37,6 +41,9 @@ def main():
     ap.add_argument("--k", type=int, help="pattern length instead of the configuration's")
     ap.add_argument("--max-errors", type=int, default=2, help="edit budget of the count (0..3; default 2)")
     ap.add_argument("--time", action="store_true", help="print the mean time of a launch (HIP events)")
+    ap.add_argument("--hits", action="store_true", help="the hits-writing kernels (ac_window_hits_device)")
+    ap.add_argument("--level-counts", action="store_true",
+                    help="with --hits: also time ac_hit_level_counts_device over the first segment's matrix")
     a = ap.parse_args()
     import torch
 
@@ -68,10 +75,14 @@ def main():
     wlen = eq if all(x is not None for x in eq) and not a.descriptors else None
     with ac.ApproxCounter(0, max_errors=a.max_errors) as c:
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        hits = None
+        if a.hits:
+            words = [ac.hits_words(s.n_kmers, s.n_windows, a.max_errors) for s in segs]
+            hits = [torch.empty(max(w, 1), dtype=torch.int32, device="cuda") for w in words]
         for i in range(a.warmup + a.launches):
             if i == a.warmup:
                 t0.record()
-            c.count_device(args.k, arr, window_len=wlen)
+            c.count_device(args.k, arr, window_len=wlen, hits=hits)
         t1.record()
         torch.cuda.synchronize()
         c.check()
@@ -79,7 +90,21 @@ def main():
               f"geometry {c.last_launch()}")
         if a.time:
             print(f"k {args.k} max_errors {a.max_errors}: {t0.elapsed_time(t1) / a.launches:.4f} ms per launch "
-                  f"({a.launches} launches after {a.warmup})")
+                  f"({a.launches} launches after {a.warmup})"
+                  + (f"; hits written per launch: {4 * sum(words)} bytes" if a.hits else ""))
+        if a.hits and a.level_counts:
+            s0 = segs[0]
+            for i in range(a.warmup + a.launches):
+                if i == a.warmup:
+                    t0.record()
+                lc = c.hit_level_counts(hits[0], s0.n_kmers, s0.n_windows, a.max_errors + 1)
+            t1.record()
+            torch.cuda.synchronize()
+            ms = t0.elapsed_time(t1) / a.launches
+            assert (lc.sum(dim=0).cpu().numpy() == s0.counts_numpy()).all(), "level counts do not sum to the counts"
+            print(f"level counts of {4 * words[0]} bytes ({s0.n_kmers} k-mers x {s0.n_windows} windows x "
+                  f"{a.max_errors + 1} levels): {ms:.4f} ms per call (memset + kernel), "
+                  f"{4 * words[0] / ms / 1e6:.1f} GB/s read")
 
 
 if __name__ == "__main__":
