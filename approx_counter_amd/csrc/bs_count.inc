@@ -101,6 +101,30 @@ __device__ __forceinline__ void bs_block4(S& s, const BsLds<K>& lds, uint32_t co
     }
 }
 
+// The flush's plane merge: the 64 / lw lanes that hold one candidate block (lanes lw apart, one per window of
+// the row) sum their planes in registers, a butterfly of bs::planes_add from 32 lanes apart down to lw --
+// one plane more per round (N before the round D lanes apart), the partner's planes through ds_bpermute
+// (the LDS crossbar: no memory, no conflict).  Every lane of the block leaves with the block's sums in
+// `m`, whose planes past the first bs::VC_PLANES come in zero.
+template <int N, uint32_t D>
+__device__ __forceinline__ void bs_merge_round(uint32_t (&m)[bs::VC_MERGED_PLANES], uint32_t lane, uint32_t lw) {
+    static_assert(N < bs::VC_MERGED_PLANES, "planes");
+    if (D >= lw) {  // (wave-uniform: rounds are skipped from the last one backwards)
+        uint32_t theirs[N];
+#pragma unroll
+        for (int b = 0; b < N; ++b) theirs[b] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((lane ^ D) << 2), (int)m[b]);
+        bs::planes_add<N>(m, theirs, m);
+    }
+}
+__device__ __forceinline__ void bs_merge(uint32_t (&m)[bs::VC_MERGED_PLANES], uint32_t lane, uint32_t lw) {
+    static_assert(bs::VC_MERGED_PLANES == bs::VC_PLANES + 5, "five rounds");
+    bs_merge_round<bs::VC_PLANES, 32u>(m, lane, lw);
+    bs_merge_round<bs::VC_PLANES + 1, 16u>(m, lane, lw);
+    bs_merge_round<bs::VC_PLANES + 2, 8u>(m, lane, lw);
+    bs_merge_round<bs::VC_PLANES + 3, 4u>(m, lane, lw);
+    bs_merge_round<bs::VC_PLANES + 4, 2u>(m, lane, lw);
+}
+
 // The state of R rows: bs_nfa.h's for the three rows of the E = 2 kernels, else bs_nfa_r.h's.
 template <int K, int R>
 struct BsNfa {
@@ -233,26 +257,23 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
     uint32_t item = n_items, row = 0u, item_end = 0u;
 
     // The workgroup's ~Eq table: wave v takes candidates 64 v .. 64 v + 63 of the group (blocks 2 v and
-    // 2 v + 1), one ballot per (position, character), in passes of 16 positions: lane 4 (i % 16) + c
-    // keeps the ballot of position i and character c and stores its two halves after the pass.  Wave 0
-    // also writes the N rows and zeroes the counts.
+    // 2 v + 1).  It parks their k-mers in its text buffer (free until the first fetch, after the table
+    // barrier); in passes of 16 positions, lane 4 (i % 16) + c reads them back -- every lane the same
+    // words: broadcast reads -- and forms the mask of position i and character c itself (bs::neq_mask: a
+    // shift, a compare and an or per candidate instead of one ballot and a masked select per (position,
+    // character) in every lane), then stores its two halves.  Wave 0 also writes the N rows and zeroes
+    // the counts.
     if (!skip && (wib == 0 || 2u * wib < LW)) {
-        const uint32_t c = g * BS_GROUP + wib * 64u + lane;
-        const bool have = wib * 64u + lane < ng;
-        const uint64_t km = have ? sg.kmers[c] : 0ull;
+        const uint32_t first = wib * 64u;
+        const uint32_t present = ng > first ? ng - first : 0u;  // (0: the blocks LW rounds up to, all ones)
+        uint64_t* park = (uint64_t*)&lds.text[wib][0][0][0];
+        park[lane] = lane < present ? sg.kmers[g * BS_GROUP + first + lane] : 0ull;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (uint32_t i0 = 0; i0 < (uint32_t)K; i0 += 16u) {
-            uint64_t mine = ~0ull;
-#pragma unroll
-            for (uint32_t i = i0; i < i0 + 16u && i < (uint32_t)K; ++i) {
-                const uint32_t ch = (uint32_t)(km >> (2u * ((uint32_t)K - 1u - i))) & 3u;
-#pragma unroll
-                for (uint32_t cc = 0; cc < 4u; ++cc) {
-                    const uint64_t bal = __ballot(!have || ch != cc);
-                    if (lane == 4u * (i - i0) + cc) mine = bal;
-                }
-            }
             const uint32_t i = i0 + (lane >> 2), cc = lane & 3u;  // (one lane per (position, character) of the pass)
+            const uint64_t mine = bs::neq_mask<K>(park, present, min(i, (uint32_t)K - 1u), cc);
             if (i < (uint32_t)K) {
                 uint32_t* p = lds.tab + (cc * CS + (i >> 2) * BS_ROW + (i & 3u) * 4u) / 4u;
                 p[(2u * wib) * 4u] = (uint32_t)mine;
@@ -281,13 +302,23 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
 
     bs::VCount vc;
     bs::vc_clear(vc);
-    // The planes' counts into the workgroup's count array (the lanes of a wave that share a candidate
-    // block, and the workgroup's waves, sum there).
+    // The planes' counts into the workgroup's count array (the workgroup's waves sum there).  The lanes of
+    // the wave that share a candidate block sum their planes in registers first (bs_merge); each then adds
+    // its own 32 LW / 64 of the block's candidates, so no two lanes of an add meet on one word.
     auto flush = [&]() __attribute__((always_inline)) {
-#pragma unroll 4
-        for (uint32_t b = 0; b < 32u; ++b) {
-            const uint32_t v = bs::vc_get(vc, b);
-            if (v) __hip_atomic_fetch_add(&lds.cnt[blk * 32u + b], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        uint32_t m[bs::VC_MERGED_PLANES];
+#pragma unroll
+        for (int b = 0; b < bs::VC_MERGED_PLANES; ++b) m[b] = b < bs::VC_PLANES ? vc.p[b < bs::VC_PLANES ? b : 0] : 0u;
+        // (the lane's place is formed here from what the row loop keeps anyway, and pinned: formed outside, the
+        // five rounds' partner addresses and the count slots are hoisted out of the row loop and held in
+        // registers through the 4-base block)
+        uint32_t w = wl, off = lane_off;
+        asm volatile("" : "+v"(w), "+v"(off));
+        bs_merge(m, (w << lwsh) | (off >> 4), LW);
+        uint32_t* cnt = &lds.cnt[2u * off + bs::merged_first(lwsh, w)];  // (block * 32 + the lane's first candidate)
+        for (uint32_t x = 0; x < bs::merged_per_lane(lwsh); ++x) {
+            const uint32_t v = bs::planes_get(m, bs::merged_first(lwsh, w) + x);
+            if (v) __hip_atomic_fetch_add(&cnt[x], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         bs::vc_clear(vc);
     };

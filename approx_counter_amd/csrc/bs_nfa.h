@@ -1,7 +1,9 @@
 // bs_nfa.h -- the bit-sliced ("candidate per bit") form of the count kernel's NFA, and the
 // bit-plane counters its hits are summed in.  Plain C++ that compiles for the
 // device (bs_count.inc) and for the host (tools/bs_nfa_check.cpp, tests/test_bs_nfa.py), so the
-// code the kernel runs is the code the CPU test checks against the oracle.
+// code the kernel runs is the code the CPU test checks against the oracle.  Also here, and checked the
+// same way (tools/bs_flush_check.cpp, tests/test_bs_flush_cpu.py): the plane adder and extraction of the
+// flush, and the ~Eq table's masks.
 //
 // The recurrence is wm_count.hip's (Wu-Manber, complemented, free start in the text), transposed:
 // bit j of a word is candidate j of a block of 32, register i is pattern position i.  The shift
@@ -23,8 +25,10 @@
 #endif
 #if defined(__clang__)
 #define AC_BS_UNROLL _Pragma("unroll")
+#define AC_BS_NOUNROLL _Pragma("nounroll")
 #else
 #define AC_BS_UNROLL  // (the host build's compiler may not know the pragma)
+#define AC_BS_NOUNROLL
 #endif
 
 namespace acamd {
@@ -178,6 +182,58 @@ AC_BS_FN uint32_t vc_get(const VCount& v, uint32_t j) {
     AC_BS_UNROLL
     for (int b = 0; b < VC_PLANES; ++b) r |= (v.p[b] >> j & 1u) << b;
     return r;
+}
+
+// The flush by plane merge (bs_count.inc): the lanes of a wave that hold the same 32 candidates -- one per
+// window of the row -- add their plane counters to each other in registers before anything goes to LDS.
+// One round of that sum is a bit-plane ripple adder: two numbers of N planes give one of N + 1, so
+// VC_PLANES planes of at most 2^VC_PLANES - 1 merged over 32 lanes (five rounds) fill VC_MERGED_PLANES.
+constexpr int VC_MERGED_PLANES = VC_PLANES + 5;
+// sum[0..N] = a[0..N-1] + b[0..N-1]; `sum` may be `a`.
+template <int N>
+AC_BS_FN void planes_add(const uint32_t* a, const uint32_t* b, uint32_t* sum) {
+    uint32_t c = a[0] & b[0];
+    sum[0] = a[0] ^ b[0];
+    AC_BS_UNROLL
+    for (int i = 1; i < N; ++i) {
+        const uint32_t x = a[i], y = b[i];
+        sum[i] = bitop3<TT_XOR3>(x, y, c);
+        c = bitop3<TT_MAJ>(x, y, c);
+    }
+    sum[N] = c;
+}
+// Candidate j's count from N planes.
+template <int N>
+AC_BS_FN uint32_t planes_get(const uint32_t (&p)[N], uint32_t j) {
+    uint32_t r = 0;
+    AC_BS_UNROLL
+    for (int b = 0; b < N; ++b) r |= (p[b] >> j & 1u) << b;
+    return r;
+}
+// After the merge every one of the 64 / LW lanes of a candidate block (LW = 1 << lwsh lanes per window)
+// holds the block's sums; lane number wl of them (its window in the row) takes the 32 LW / 64 candidates
+// from merged_first(lwsh, wl) on, so each (block, candidate) is added to LDS by one lane.
+AC_BS_FN uint32_t merged_per_lane(uint32_t lwsh) { return 32u >> (6u - lwsh); }
+AC_BS_FN uint32_t merged_first(uint32_t lwsh, uint32_t wl) { return wl * merged_per_lane(lwsh); }
+
+// The workgroup's ~Eq table (bs_count.inc), one (position, character) of up to 64 candidates: bit j is set
+// iff candidate j's base at pattern position i (0 = first base: the k-mer's highest two bits) differs from
+// character c (0..3), or slot j is past the n candidates present -- `km` holds 64 slots, those past n are
+// not looked at.
+template <int K>
+AC_BS_FN uint64_t neq_mask(const uint64_t* km, uint32_t n, uint32_t i, uint32_t c) {
+    const uint32_t sh = 2u * ((uint32_t)K - 1u - i);
+    uint32_t lo = 0u, hi = 0u;
+    AC_BS_NOUNROLL  // (eight slots of each half at a time: unrolled whole, the 64 reads are all hoisted and spill)
+    for (int j0 = 24; j0 >= 0; j0 -= 8) {
+        AC_BS_UNROLL
+        for (int j = j0 + 7; j >= j0; --j) {
+            lo = lo << 1 | (((uint32_t)(km[j] >> sh) & 3u) != c ? 1u : 0u);
+            hi = hi << 1 | (((uint32_t)(km[j + 32] >> sh) & 3u) != c ? 1u : 0u);
+        }
+    }
+    const uint64_t m = (uint64_t)hi << 32 | lo;
+    return n < 64u ? m | ~0ull << n : m;
 }
 
 }  // namespace bs
