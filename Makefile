@@ -35,7 +35,7 @@ CAPI := capi count_launch capi_exact capi_comm
 HOSTONLY := host_pack stage_plan
 HDRS := $(INC)/approx_counter_amd.h $(INC)/approx_counter_amd_testing.h $(CSRC)/wm_count.h $(CSRC)/exact_count.h \
 	$(CSRC)/host_pack.h $(CSRC)/nrec.h $(CSRC)/ctx.h $(CSRC)/stage_plan.h $(CSRC)/bs_nfa.h $(CSRC)/bs_nfa_r.h \
-	$(CSRC)/hit_levels.h
+	$(CSRC)/hit_levels.h $(CSRC)/bs_pos.h
 INCS := -I$(INC) -I$(CSRC)
 # host-only code that includes the HIP headers (no kernel, no <<<>>>)
 HIP_HOST := -D__HIP_PLATFORM_AMD__ -I$(ROCM_PATH)/include
@@ -73,6 +73,11 @@ $(OBJDIR)/bsh_count.o: $(CSRC)/bsh_count.hip $(CSRC)/stage_dev.inc $(CSRC)/count
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) -c $< -o $@
 
+# the hits-and-positions family (and the position-profile kernel), likewise
+$(OBJDIR)/bsp_count.o: $(CSRC)/bsp_count.hip $(CSRC)/stage_dev.inc $(CSRC)/count_frame.inc $(CSRC)/bs_count.inc $(HDRS)
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) -c $< -o $@
+
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(INCS) -c $< -o $@
@@ -91,7 +96,7 @@ $(HOSTONLY:%=$(OBJDIR)/%.o): $(OBJDIR)/%.o: $(CSRC)/%.cpp $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(CXX) $(HOST_CXXFLAGS) $(HIP_HOST) $(INCS) -c $< -o $@
 
-$(LIB): $(OBJDIR)/wm_count.o $(OBJDIR)/bs3_count.o $(OBJDIR)/bsh_count.o $(OBJDIR)/exact_count.o $(OBJDIR)/jobs_stage.o $(CAPI:%=$(OBJDIR)/%.o) $(HOSTONLY:%=$(OBJDIR)/%.o)
+$(LIB): $(OBJDIR)/wm_count.o $(OBJDIR)/bs3_count.o $(OBJDIR)/bsh_count.o $(OBJDIR)/bsp_count.o $(OBJDIR)/exact_count.o $(OBJDIR)/jobs_stage.o $(CAPI:%=$(OBJDIR)/%.o) $(HOSTONLY:%=$(OBJDIR)/%.o)
 	@mkdir -p $(dir $@)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -pthread
 
@@ -99,7 +104,7 @@ $(HOSTLIB): $(HOST_SRC) $(HOSTDIR)/host_capi.cpp $(HOST_HDRS)
 	@mkdir -p $(LIBDIR)
 	$(CXX) $(HOST_CXXFLAGS) -Iinclude -I$(HOSTDIR) -shared -o $@ $(HOST_SRC) $(HOSTDIR)/host_capi.cpp
 
-$(CLI): $(HOSTDIR)/adaptfinder.cpp $(HOST_SRC) $(HOST_HDRS) $(CSRC)/hit_levels.h $(CSRC)/bs_nfa.h $(LIB)
+$(CLI): $(HOSTDIR)/adaptfinder.cpp $(HOST_SRC) $(HOST_HDRS) $(CSRC)/hit_levels.h $(CSRC)/bs_nfa.h $(CSRC)/bs_nfa_r.h $(CSRC)/bs_pos.h $(LIB)
 	@mkdir -p $(BINDIR)
 	$(CXX) $(HOST_CXXFLAGS) -Iinclude -I$(HOSTDIR) -o $@ $(HOSTDIR)/adaptfinder.cpp $(HOST_SRC) \
 		-L$(LIBDIR) -lapprox_counter_amd -Wl,-rpath,'$$ORIGIN/../lib' -pthread
@@ -112,6 +117,7 @@ asm: $(WM_SRC) $(HDRS)
 	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) --cuda-device-only -S $< -o build/asm/wm_count.s
 	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) --cuda-device-only -S $(CSRC)/bs3_count.hip -o build/asm/bs3_count.s
 	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) --cuda-device-only -S $(CSRC)/bsh_count.hip -o build/asm/bsh_count.s
+	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) --cuda-device-only -S $(CSRC)/bsp_count.hip -o build/asm/bsp_count.s
 
 clean:
 	rm -rf build $(LIBDIR) $(BINDIR) oracle/_build

@@ -154,6 +154,19 @@ def load():
         L.ac_window_hits_samples.restype = ctypes.c_int
         L.ac_hit_level_counts_device.argtypes = [vp, p32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, p32, vp]
         L.ac_hit_level_counts_device.restype = ctypes.c_int
+    if hasattr(L, "ac_window_positions_words"):  # (likewise the match end positions)
+        pp32 = ctypes.POINTER(p32)
+        L.ac_window_positions_words.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
+        L.ac_window_positions_words.restype = ctypes.c_uint64
+        L.ac_window_positions_device.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ACSegment), ctypes.c_uint32, p32, pp32,
+                                                 pp32, vp]
+        L.ac_window_positions_device.restype = ctypes.c_int
+        L.ac_window_positions_samples.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ACSampleJob), ctypes.c_uint32, pp32,
+                                                  pp32]
+        L.ac_window_positions_samples.restype = ctypes.c_int
+        L.ac_hit_position_profile_device.argtypes = [vp, p32, p32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                                     ctypes.c_uint32, p32, vp]
+        L.ac_hit_position_profile_device.restype = ctypes.c_int
     L.ac_exact_path.argtypes = [vp]
     L.ac_exact_path.restype = ctypes.c_int
     pint = ctypes.POINTER(ctypes.c_int)

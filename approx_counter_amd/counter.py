@@ -136,14 +136,66 @@ def distances_from_hits(hit) -> np.ndarray:
     return (hit.shape[0] - hit.sum(axis=0)).astype(np.uint8)
 
 
+def positions_words(n_kmers: int, n_windows: int) -> int:
+    """ac_window_positions_words: the u32 words of one segment's position matrix, 8 x n_windows x ceil(n_kmers / 32)."""
+    return 8 * int(n_windows) * ((int(n_kmers) + 31) // 32)
+
+
+def unpack_positions(planes, hit_E, n_kmers: int) -> np.ndarray:
+    """A position matrix's values: `planes` is (8, n_windows, words) uint32, plane b holding bit b of
+    pos - 1; `hit_E` is bool (n_windows, n_kmers), the pairs within the budget (level E of the hit
+    matrix).  Returns int16 (n_windows, n_kmers): the exclusive end offset 1..L of the leftmost occurrence
+    at the best distance, -1 where hit_E is False.  Pure numpy."""
+    pl = np.ascontiguousarray(planes, dtype="<u4")
+    if pl.ndim != 3 or pl.shape[0] != 8 or pl.shape[2] != (int(n_kmers) + 31) // 32:
+        raise ValueError("position matrix must be (8, n_windows, ceil(n_kmers / 32))")
+    hit_E = np.asarray(hit_E, dtype=bool)
+    if hit_E.shape != (pl.shape[1], int(n_kmers)):
+        raise ValueError("hit_E must be (n_windows, n_kmers)")
+    bits = np.unpackbits(pl.view(np.uint8).reshape(8, pl.shape[1], pl.shape[2] * 4), axis=-1,
+                         bitorder="little")[:, :, : int(n_kmers)]
+    pos = np.zeros(hit_E.shape, dtype=np.int16)
+    for b in range(8):
+        pos |= bits[b].astype(np.int16) << b
+    return np.where(hit_E, pos + 1, -1).astype(np.int16)
+
+
 class WindowHits:
     """One part's counts and hit levels (ac_window_hits_samples): which windows hold each k-mer within
-    0..E edits -- the reference's tcount[errors][read] (approx_counter.cpp:553-565) before it is summed."""
+    0..E edits -- the reference's tcount[errors][read] (approx_counter.cpp:553-565) before it is summed.
+    From window_hits(..., positions=True) also the match end positions (ac_window_positions_samples)."""
 
-    def __init__(self, counts, levels, n_kmers: int):
+    def __init__(self, counts, levels, n_kmers: int, planes=None, window_len: int = 0, counter=None):
         self.counts = counts
         self.levels = np.asarray(levels, dtype=np.uint32)  # (E + 1, n_windows, words)
         self.n_kmers = int(n_kmers)
+        self.planes = None if planes is None else np.asarray(planes, dtype=np.uint32)  # (8, n_windows, words)
+        self.window_len = int(window_len)
+        self._counter = counter
+
+    def end_positions(self) -> np.ndarray:
+        """int16 (n_windows, n_kmers): where the leftmost occurrence at the best distance ends (exclusive,
+        1..L), -1 where the window does not hold the k-mer within E edits."""
+        if self.planes is None:
+            raise ValueError("no positions: ask window_hits(..., positions=True)")
+        return unpack_positions(self.planes, self.hit(self.max_errors), self.n_kmers)
+
+    def position_profile(self) -> np.ndarray:
+        """uint32 (E + 1, n_kmers, L): the windows at distance exactly d whose best occurrence ends at base
+        p + 1, computed on the device (ac_hit_position_profile_device)."""
+        import torch
+
+        if self.planes is None or self._counter is None:
+            raise ValueError("no positions: ask window_hits(..., positions=True)")
+        lv, nw, _ = self.levels.shape
+        if not (self.n_kmers and nw):
+            return np.zeros((lv, self.n_kmers, self.window_len), np.uint32)
+        dev = torch.device("cuda")
+        h = torch.from_numpy(self.levels.view(np.int32)).to(dev)
+        p = torch.from_numpy(self.planes.view(np.int32)).to(dev)
+        out = self._counter.hit_position_profile(h, p, self.n_kmers, nw, lv, self.window_len)
+        torch.cuda.synchronize(dev)
+        return out.cpu().numpy().view(np.uint32)
 
     @property
     def max_errors(self) -> int:
@@ -399,14 +451,17 @@ class ApproxCounter:
         """ac_error_count_samples: [(kmers, device sample from upload_sample), ...], one fused launch."""
         return self._sample_jobs(self._L.ac_error_count_samples, k, parts)
 
-    def window_hits(self, k: int, parts) -> list:
+    def window_hits(self, k: int, parts, positions: bool = False) -> list:
         """ac_window_hits_samples: [(kmers, PackedSample), ...] (up to 4 parts, e.g. both read ends) are
         uploaded into the context's sample slots and counted in one fused launch that also writes every
         window's hit levels; returns one WindowHits per part.  Only where the bit-sliced kernel counts
         (k = 16 or 18..32, equal windows of 1..256 bases, a single-device context), at the context's
-        edit budget; anything else raises (AC_ERR_INVALID)."""
+        edit budget; anything else raises (AC_ERR_INVALID).  positions: ac_window_positions_samples -- every
+        WindowHits also holds the match end positions (.end_positions(), .position_profile())."""
         if not hasattr(self._L, "ac_window_hits_samples"):
             raise _lib.ApproxCounterError(_lib.AC_ERR_INVALID, "this build of the library has no ac_window_hits_samples")
+        if positions:
+            return self._window_positions(k, parts)
         E = self.max_errors
         keep, arr, mats = [], [], []
         for slot, (km, smp) in enumerate(parts):
@@ -423,6 +478,40 @@ class ApproxCounter:
         check(self._L.ac_window_hits_samples(self._h, int(k), a, len(arr), hp), self._h)
         return [WindowHits(c[: km.size], m[: hits_words(km.size, nw, E)].reshape(E + 1, nw, (km.size + 31) // 32), km.size)
                 for (km, c, nw), m in zip(keep, mats)]
+
+    def _window_positions(self, k: int, parts) -> list:
+        if not hasattr(self._L, "ac_window_positions_samples"):
+            raise _lib.ApproxCounterError(_lib.AC_ERR_INVALID,
+                                          "this build of the library has no ac_window_positions_samples")
+        E = self.max_errors
+        keep, arr, mats, planes = [], [], [], []
+        for slot, (km, smp) in enumerate(parts):
+            km = np.ascontiguousarray(np.asarray(km, dtype=np.uint64))
+            c = np.zeros(max(km.size, 1), dtype=np.uint64)
+            mats.append(np.full(max(hits_words(km.size, smp.n_windows, E), 1), 0xFFFFFFFF, dtype=np.uint32))
+            planes.append(np.full(max(positions_words(km.size, smp.n_windows), 1), 0xFFFFFFFF, dtype=np.uint32))
+            keep.append((km, c, smp.n_windows, int(smp.length[0]) if smp.n_windows else 0))
+            arr.append(ACSampleJob(_ptr(km if km.size else np.zeros(1, np.uint64), ctypes.c_uint64), int(km.size),
+                                   self.upload_sample(smp, slot), _ptr(c, ctypes.c_uint64)))
+        a = (ACSampleJob * len(arr))(*arr)
+        hp = (_lib.p32 * len(arr))(*[_ptr(m, ctypes.c_uint32) for m in mats])
+        pp = (_lib.p32 * len(arr))(*[_ptr(m, ctypes.c_uint32) for m in planes])
+        check(self._L.ac_window_positions_samples(self._h, int(k), a, len(arr), hp, pp), self._h)
+        return [WindowHits(c[: km.size], m[: hits_words(km.size, nw, E)].reshape(E + 1, nw, (km.size + 31) // 32), km.size,
+                           p[: positions_words(km.size, nw)].reshape(8, nw, (km.size + 31) // 32), L, self)
+                for (km, c, nw, L), m, p in zip(keep, mats, planes)]
+
+    def hit_position_profile(self, hits, pos, n_kmers: int, n_windows: int, levels: int, window_len: int, stream=None):
+        """ac_hit_position_profile_device over a device hit matrix (`levels` planes) and its position
+        matrix (8 planes), torch tensors: returns an int32 device tensor (levels, n_kmers, window_len), the
+        windows at distance exactly d whose best occurrence ends at base p + 1 (asynchronous)."""
+        import torch
+
+        out = torch.empty((int(levels), max(int(n_kmers), 1), int(window_len)), dtype=torch.int32, device=hits.device)
+        p = lambda t: ctypes.cast(ctypes.c_void_p(t.data_ptr()), _lib.p32)  # noqa: E731
+        check(self._L.ac_hit_position_profile_device(self._h, p(hits), p(pos), int(n_kmers), int(n_windows), int(levels),
+                                                     int(window_len), p(out), ctypes.c_void_p(stream or 0)), self._h)
+        return out[:, : int(n_kmers)]
 
     def hit_level_counts(self, hits, n_kmers: int, n_windows: int, levels: int, stream=None):
         """ac_hit_level_counts_device over a device hit matrix (a torch tensor of `levels` planes): returns
@@ -495,14 +584,16 @@ class ApproxCounter:
         count_device (saves the per-call ctypes marshalling in launch loops)."""
         return (ACSegment * len(segments))(*[s.as_struct() for s in segments])
 
-    def count_device(self, k: int, segments, stream=None, accumulate: bool = False, window_len=None, hits=None) -> None:
+    def count_device(self, k: int, segments, stream=None, accumulate: bool = False, window_len=None, hits=None,
+                     positions=None) -> None:
         """ac_error_count_device over DeviceSegment objects, or an array from
         segment_array (asynchronous).  window_len (one per segment): the samples'
         windows all have that length and sit back to back at ceil32 strides
         (start / length are not read).  accumulate: AC_DEVICE_ACCUMULATE.
         hits (one device tensor per segment, hits_words(...) int32 / uint32 words each; None for a segment
         without work): ac_window_hits_device -- the same launch also writes the windows' hit levels
-        (window_len required, no accumulate)."""
+        (window_len required, no accumulate).  positions (with hits; one device tensor per segment,
+        positions_words(...) words each): ac_window_positions_device -- and the match end positions."""
         arr = segments if isinstance(segments, ctypes.Array) else self.segment_array(segments)
         wp = None
         if window_len is not None:
@@ -517,7 +608,17 @@ class ApproxCounter:
                 raise ValueError("one hits tensor per segment")
             hp = (_lib.p32 * len(arr))(*[ctypes.cast(ctypes.c_void_p(h.data_ptr() if h is not None else 0), _lib.p32)
                                          for h in hits])
-            st = self._L.ac_window_hits_device(self._h, int(k), arr, len(arr), wp, hp, ctypes.c_void_p(stream or 0))
+            if positions is not None:
+                if len(positions) != len(arr):
+                    raise ValueError("one positions tensor per segment")
+                pp = (_lib.p32 * len(arr))(*[ctypes.cast(ctypes.c_void_p(h.data_ptr() if h is not None else 0), _lib.p32)
+                                             for h in positions])
+                st = self._L.ac_window_positions_device(self._h, int(k), arr, len(arr), wp, hp, pp,
+                                                        ctypes.c_void_p(stream or 0))
+            else:
+                st = self._L.ac_window_hits_device(self._h, int(k), arr, len(arr), wp, hp, ctypes.c_void_p(stream or 0))
+        elif positions is not None:
+            raise ValueError("positions come with hits")
         else:
             st = self._L.ac_error_count_device(self._h, int(k), arr, len(arr), wp, 1 if accumulate else 0,
                                                ctypes.c_void_p(stream or 0))

@@ -1,6 +1,7 @@
 // bs_count.inc -- the bit-sliced count kernel's body (DESIGN.md §4e), included by wm_count.hip (three NFA
-// rows: edit budgets 0..2), by bs3_count.hip (four rows: budget 3) and by bsh_count.hip (either, and the
-// windows' hit words stored beside the counts) inside their anonymous namespaces:
+// rows: edit budgets 0..2), by bs3_count.hip (four rows: budget 3), by bsh_count.hip (either, and the
+// windows' hit words stored beside the counts) and by bsp_count.hip (either, the hit words and the match end
+// positions) inside their anonymous namespaces:
 // the NFA's place in the frame of count_frame.inc (deal, staged prologue,
 // sub-queues, gate, count hand-off -- the word-parallel kernel's), with another mapping of a wave
 // onto the work.
@@ -74,19 +75,40 @@ __device__ __forceinline__ uint32_t bs_row(uint32_t code, uint32_t nm, uint32_t 
 // kernels, wm_count.h BS3_ONE_BASE_K): one base's table rows are held at a time -- a base's reads are
 // issued when the previous base's rows have been used, K registers less; the SIMD's other wave covers
 // the reads.
+// A state S = BsWithPos<..> (the POS kernels of bsp_count.hip) carries the position planes (bs_pos.h), the
+// block's number and the launch's E: its hits are accumulated per base (bs::hits_new), the candidates newly
+// hit at a base written into the planes, the planes of the block's number at its end.  Any other state:
+// hits in pairs, as above.
+template <class B>
+struct BsWithPos : B {
+    bs::PosPlanes ps;
+    uint32_t q, budget;  // (wave-uniform)
+};
+template <class S>
+struct BsPosOf {
+    static constexpr bool ON = false;
+};
+template <class B>
+struct BsPosOf<BsWithPos<B>> {
+    static constexpr bool ON = true;
+};
 template <int K, bool AHEAD2, class S>
 __device__ __forceinline__ void bs_block4(S& s, const BsLds<K>& lds, uint32_t code, uint32_t nm, uint32_t ncode,
                                           uint32_t nnm, uint32_t lane_off, uint32_t (&ea)[K]) {
+    constexpr bool POS = BsPosOf<S>::ON;
     if constexpr (!AHEAD2) {
 #pragma unroll
         for (uint32_t b = 0; b < 4u; b += 2u) {
             bs::advance<K>(s, ea);
             const auto x = bs::last<K>(s);
+            if constexpr (POS) bs::pos_base(s.ps, bs::hits_new(s, s.budget), b);
             bs_read<K>(lds, bs_row<K>(code, nm, b + 1u, lane_off), ea);
             bs::advance<K>(s, ea);
-            bs::hits2<K>(s, x);
+            if constexpr (POS) bs::pos_base(s.ps, bs::hits_new(s, s.budget), b + 1u);
+            else bs::hits2<K>(s, x);
             bs_read<K>(lds, b + 2u < 4u ? bs_row<K>(code, nm, b + 2u, lane_off) : bs_row<K>(ncode, nnm, 0u, lane_off), ea);
         }
+        if constexpr (POS) bs::pos_block(s.ps, s.q);
         return;
     }
     uint32_t eb[K];
@@ -95,10 +117,13 @@ __device__ __forceinline__ void bs_block4(S& s, const BsLds<K>& lds, uint32_t co
         bs_read<K>(lds, bs_row<K>(code, nm, b + 1u, lane_off), eb);
         bs::advance<K>(s, ea);
         const auto x = bs::last<K>(s);
+        if constexpr (POS) bs::pos_base(s.ps, bs::hits_new(s, s.budget), b);
         bs_read<K>(lds, b + 2u < 4u ? bs_row<K>(code, nm, b + 2u, lane_off) : bs_row<K>(ncode, nnm, 0u, lane_off), ea);
         bs::advance<K>(s, eb);
-        bs::hits2<K>(s, x);
+        if constexpr (POS) bs::pos_base(s.ps, bs::hits_new(s, s.budget), b + 1u);
+        else bs::hits2<K>(s, x);
     }
+    if constexpr (POS) bs::pos_block(s.ps, s.q);
 }
 
 // The flush's plane merge: the 64 / lw lanes that hold one candidate block (lanes lw apart, one per window of
@@ -135,15 +160,28 @@ struct BsNfa<K, 3> {
     typedef bs::State<K> State;
 };
 
+// ... and with the position planes beside them (POS).
+template <int K, int R, bool POS>
+struct BsState {
+    typedef typename BsNfa<K, R>::State type;
+};
+template <int K, int R>
+struct BsState<K, R, true> {
+    typedef BsWithPos<typename BsNfa<K, R>::State> type;
+};
+
 // R = 3: the edit budget E = a.max_errors is 0, 1 or 2 (a smaller budget drops levels where a row's
 // hit masks become counts); R = 4: E = 3.
 // HITS (bsh_count.hip, plain launches; DESIGN.md §4e "Hit levels"): where a row's masks become counts,
 // every lane whose window and candidate block exist also stores its hit word of each level 0..E to the
 // segment's matrix a.hits[si] -- one word, one lane, one row: no memset, no atomic.
-template <int K, bool STAGED, int R = 3, bool HITS = false>
+// POS (bsp_count.hip, implies HITS; DESIGN.md §4e "Match end positions"): the same lanes also store the
+// eight plane words of their candidates' end positions to a.pos[si], masked to the pairs with a hit.
+template <int K, bool STAGED, int R = 3, bool HITS = false, bool POS = false>
 __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
     static_assert(K >= 3 && K <= 32, "a k-mer is one 64-bit word (dna2int layout: K = 32 fills it)");
     static_assert(!(HITS && STAGED), "the staged instantiations do not write hits");
+    static_assert(HITS || !POS, "positions come with the hits");
     constexpr uint32_t CS = BsLds<K>::CHAR_STRIDE;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -386,8 +424,12 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
             const uint32_t nmw = row_n ? text[16u + (gc >> 1)] >> ((gc & 1u) * 16u) : 0u;
             return (nmw | (0xffffu << real)) & 0xffffu;
         };
-        typename BsNfa<K, R>::State s;
+        typename BsState<K, R, POS>::type s;
         bs::init<K>(s);
+        if constexpr (POS) {
+            bs::pos_clear(s.ps);
+            s.budget = budget;
+        }
         uint32_t code = text[0], nm = n_word(0u);
         uint32_t ea[K];
         bs_read<K>(lds, bs_row<K>(code, nm, 0u, lane_off), ea);
@@ -412,12 +454,13 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
                 // (read again, so that the rows read ahead are not kept in registers across this)
                 bs_read<K>(lds, bs_row<K>(code, nm, 0u, lane_off), ea);
             }
+            if constexpr (POS) s.q = q;
             uint32_t ncode = code >> 8, nnm = nm >> 4;
             if ((q & 3u) == 3u) {
                 ncode = text[(q >> 2) + 1u];
                 nnm = n_word((q >> 2) + 1u);
             }
-            bs_block4<K, !(R == 4 && K >= BS3_ONE_BASE_K)>(s, lds, code, nm, ncode, nnm, lane_off, ea);
+            bs_block4<K, !(R == 4 && K >= (POS ? BSP3_ONE_BASE_K : BS3_ONE_BASE_K))>(s, lds, code, nm, ncode, nnm, lane_off, ea);
             code = ncode;
             nm = nnm;
         }
@@ -443,6 +486,17 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
                 } else {
 #pragma unroll
                     for (int e = 0; e < R; ++e) hp[(uint64_t)e * plane] = ~s.a[e] & keep;
+                }
+                if constexpr (POS) {
+                    // Plane b's word: bit j = bit b of pos - 1 of candidate j and this window, 0 where the
+                    // pair has no hit within the budget.
+                    uint32_t aE;
+                    if constexpr (R == 3) aE = budget >= 2u ? s.a2 : budget == 1u ? s.a1 : s.a0;
+                    else aE = s.a[R - 1];
+                    const uint32_t hit = ~aE & keep;
+                    uint32_t* pp = a.pos[si] + (uint64_t)(row * wpr + wl) * words + (BS_GROUP / 32u) * g + blk;
+#pragma unroll
+                    for (int b = 0; b < bs::POS_PLANES; ++b) pp[(uint64_t)b * plane] = s.ps.p[b] & hit;
                 }
             }
         }

@@ -13,6 +13,7 @@
 
 #include "bs_nfa.h"
 #include "bs_nfa_r.h"
+#include "bs_pos.h"
 #include "hit_levels.h"
 #include "nrec.h"
 #include "wm_count.h"

@@ -287,6 +287,7 @@ void ac_destroy(ac_ctx* ctx) {
         if (p) (void)hipFree(p);
     if (ctx->d_stage) (void)hipFree(ctx->d_stage);
     if (ctx->d_hits) (void)hipFree(ctx->d_hits);
+    if (ctx->d_pos) (void)hipFree(ctx->d_pos);
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
     for (auto& sc : ctx->sc) {
         if (sc.queue) (void)hipFree(sc.queue);
@@ -549,9 +550,10 @@ ac_status ac_count(ac_ctx* ctx, uint32_t k, const uint64_t* kmers, uint32_t n_km
 }
 
 
-// ac_error_count_samples, and -- hits_host: one host matrix per job -- ac_window_hits_samples.
+// ac_error_count_samples, and -- hits_host: one host matrix per job -- ac_window_hits_samples, and --
+// pos_host beside it -- ac_window_positions_samples.
 static ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, uint32_t n_jobs,
-                               uint32_t* const* hits_host) {
+                               uint32_t* const* hits_host, uint32_t* const* pos_host = nullptr) {
     if (!ctx) return fail(nullptr, AC_ERR_INVALID, "ctx is NULL");
     if (ac_status st = check_k(ctx, k)) return st;
     if (n_jobs > AC_MAX_JOBS) return fail(ctx, AC_ERR_INVALID, "too many jobs in one call (max 4)");
@@ -589,6 +591,8 @@ static ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* job
     // device matrices, back to back in one block
     uint32_t* d_hits[AC_MAX_JOBS] = {};
     size_t hits_bytes[AC_MAX_JOBS] = {};
+    uint32_t* d_pos[AC_MAX_JOBS] = {};
+    size_t pos_bytes[AC_MAX_JOBS] = {};
     if (hits_host) {
         bool live[AC_MAX_JOBS];
         for (uint32_t j = 0; j < n_jobs; ++j) live[j] = jobs[j].n_kmers && jobs[j].sample.n_windows;
@@ -601,12 +605,26 @@ static ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* job
             if (live[j] && !hits_host[j]) return fail(ctx, AC_ERR_INVALID, "window hits: hits_host[j] is NULL for a job with work");
             all += align256(hits_bytes[j]);
         }
+        size_t all_pos = 0;
+        if (pos_host)
+            for (uint32_t j = 0; j < n_jobs; ++j) {
+                pos_bytes[j] = sizeof(uint32_t) * (size_t)ac_window_positions_words(jobs[j].n_kmers, jobs[j].sample.n_windows);
+                if (live[j] && !pos_host[j])
+                    return fail(ctx, AC_ERR_INVALID, "window positions: pos_host[j] is NULL for a job with work");
+                all_pos += align256(pos_bytes[j]);
+            }
         AC_HIP(ctx, hipSetDevice(ctx->device));
         if (ac_status s2 = grow(ctx, &ctx->d_hits, &ctx->d_hits_cap, all)) return s2;
-        size_t at = 0;
+        if (pos_host)
+            if (ac_status s2 = grow(ctx, &ctx->d_pos, &ctx->d_pos_cap, all_pos)) return s2;
+        size_t at = 0, at_pos = 0;
         for (uint32_t j = 0; j < n_jobs; ++j) {
             d_hits[j] = (uint32_t*)((char*)ctx->d_hits + at);
             at += align256(hits_bytes[j]);
+            if (pos_host) {
+                d_pos[j] = (uint32_t*)((char*)ctx->d_pos + at_pos);
+                at_pos += align256(pos_bytes[j]);
+            }
         }
     }
     AC_HIP(ctx, hipSetDevice(ctx->device));
@@ -628,7 +646,7 @@ static ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* job
         base += jobs[j].n_kmers;
     }
     if (ac_status rc = launch(ctx, k, seg, n_jobs, st, true, nullptr, 0, 0, no_n, ulen, nullptr, nullptr,
-                              hits_host ? d_hits : nullptr))
+                              hits_host ? d_hits : nullptr, hits_host && pos_host ? d_pos : nullptr))
         return rc;
     ctx->h_counts.resize(total);
     AC_HIP(ctx, hipMemcpyAsync(ctx->h_counts.data(), ctx->d_buf[5], sizeof(uint32_t) * total, hipMemcpyDeviceToHost, st));
@@ -636,6 +654,10 @@ static ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* job
         for (uint32_t j = 0; j < n_jobs; ++j)
             if (jobs[j].n_kmers && jobs[j].sample.n_windows)
                 AC_HIP(ctx, hipMemcpyAsync(hits_host[j], d_hits[j], hits_bytes[j], hipMemcpyDeviceToHost, st));
+    if (hits_host && pos_host)
+        for (uint32_t j = 0; j < n_jobs; ++j)
+            if (jobs[j].n_kmers && jobs[j].sample.n_windows)
+                AC_HIP(ctx, hipMemcpyAsync(pos_host[j], d_pos[j], pos_bytes[j], hipMemcpyDeviceToHost, st));
     if (ac_status rc = ac_check(ctx, st)) return rc;  // synchronises the stream
     base = 0;
     for (uint32_t j = 0; j < n_jobs; ++j)
@@ -651,11 +673,15 @@ uint64_t ac_window_hits_words(uint32_t n_kmers, uint32_t n_windows, uint32_t max
     return (uint64_t)(max_errors + 1u) * n_windows * (((uint64_t)n_kmers + 31u) / 32u);
 }
 
-ac_status ac_window_hits_device(ac_ctx* ctx, uint32_t k, const ac_segment* segments, uint32_t n_segments,
-                                const uint32_t* window_len, uint32_t* const* hits, void* hip_stream) {
+// ac_window_hits_device, and -- with_pos: one position matrix per segment beside the hits --
+// ac_window_positions_device.
+static ac_status window_hits_device(ac_ctx* ctx, uint32_t k, const ac_segment* segments, uint32_t n_segments,
+                                    const uint32_t* window_len, uint32_t* const* hits, bool with_pos, uint32_t* const* pos,
+                                    void* hip_stream) {
     if (!ctx) return fail(nullptr, AC_ERR_INVALID, "ctx is NULL");
     if (n_segments > AC_MAX_SEGS) return fail(ctx, AC_ERR_INVALID, "too many segments in one launch (max 4)");
     if (n_segments && !hits) return fail(ctx, AC_ERR_INVALID, "window hits: hits is NULL");
+    if (with_pos && n_segments && !pos) return fail(ctx, AC_ERR_INVALID, "window positions: pos is NULL");
     uint32_t ul[AC_MAX_SEGS];
     if (window_len)
         for (uint32_t i = 0; i < n_segments; ++i) {
@@ -665,7 +691,45 @@ ac_status ac_window_hits_device(ac_ctx* ctx, uint32_t k, const ac_segment* segme
     static uint32_t* const none[AC_MAX_SEGS] = {};
     AC_HIP(ctx, hipSetDevice(ctx->device));
     return launch(ctx, k, segments, n_segments, (hipStream_t)hip_stream, true, nullptr, 0, 0, nullptr,
-                  window_len ? ul : nullptr, nullptr, nullptr, hits ? hits : none);
+                  window_len ? ul : nullptr, nullptr, nullptr, hits ? hits : none, with_pos ? (pos ? pos : none) : nullptr);
+}
+
+ac_status ac_window_hits_device(ac_ctx* ctx, uint32_t k, const ac_segment* segments, uint32_t n_segments,
+                                const uint32_t* window_len, uint32_t* const* hits, void* hip_stream) {
+    return window_hits_device(ctx, k, segments, n_segments, window_len, hits, false, nullptr, hip_stream);
+}
+
+uint64_t ac_window_positions_words(uint32_t n_kmers, uint32_t n_windows) {
+    return 8ull * n_windows * (((uint64_t)n_kmers + 31u) / 32u);
+}
+
+ac_status ac_window_positions_device(ac_ctx* ctx, uint32_t k, const ac_segment* segments, uint32_t n_segments,
+                                     const uint32_t* window_len, uint32_t* const* hits, uint32_t* const* pos,
+                                     void* hip_stream) {
+    return window_hits_device(ctx, k, segments, n_segments, window_len, hits, true, pos, hip_stream);
+}
+
+ac_status ac_window_positions_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, uint32_t n_jobs,
+                                      uint32_t* const* hits_host, uint32_t* const* pos_host) {
+    if (!ctx) return fail(nullptr, AC_ERR_INVALID, "ctx is NULL");
+    if (n_jobs && !hits_host) return fail(ctx, AC_ERR_INVALID, "window hits: hits_host is NULL");
+    if (n_jobs && !pos_host) return fail(ctx, AC_ERR_INVALID, "window positions: pos_host is NULL");
+    static uint32_t* const none[AC_MAX_JOBS] = {};
+    return count_samples(ctx, k, jobs, n_jobs, hits_host ? hits_host : none, pos_host ? pos_host : none);
+}
+
+ac_status ac_hit_position_profile_device(ac_ctx* ctx, const uint32_t* hits, const uint32_t* pos, uint32_t n_kmers,
+                                         uint32_t n_windows, uint32_t levels, uint32_t window_len, uint32_t* profile,
+                                         void* hip_stream) {
+    if (!ctx) return fail(nullptr, AC_ERR_INVALID, "ctx is NULL");
+    if (levels < 1u || levels > 4u) return fail(ctx, AC_ERR_INVALID, "position profile: levels must be 1..4");
+    if (window_len < 1u || window_len > 256u) return fail(ctx, AC_ERR_INVALID, "position profile: window_len must be 1..256");
+    if (n_kmers && !profile) return fail(ctx, AC_ERR_INVALID, "position profile: profile is NULL");
+    if (n_kmers && n_windows && (!hits || !pos)) return fail(ctx, AC_ERR_INVALID, "position profile: hits or pos is NULL");
+    AC_HIP(ctx, hipSetDevice(ctx->device));
+    AC_HIP(ctx, acamd::launch_hit_position_profile(hits, pos, n_kmers, n_windows, levels, window_len, profile,
+                                                   (hipStream_t)hip_stream));
+    return AC_OK;
 }
 
 ac_status ac_window_hits_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, uint32_t n_jobs,

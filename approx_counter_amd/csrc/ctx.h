@@ -31,6 +31,9 @@ struct ac_ctx {
     // ac_window_hits_samples: the jobs' device hit matrices, one block (grow-only)
     void* d_hits = nullptr;
     size_t d_hits_cap = 0;
+    // ac_window_positions_samples: the jobs' device position matrices, likewise
+    void* d_pos = nullptr;
+    size_t d_pos_cap = 0;
     // ac_error_count staging: the inputs packed back to back in pinned host
     // memory, one H2D copy into d_stage, counts copied back into the same
     // pinned block (grow-only)
@@ -87,6 +90,7 @@ struct ac_ctx {
     uint32_t resident_bs3[2][33] = {};           // the same for the E = 3 kernels (bs3_count.hip), each queried
                                                  // at its first launch
     uint32_t resident_bsh[2][33] = {};           // the hits-writing kernels (bsh_count.hip): [E == 3][k]
+    uint32_t resident_bsp[2][33] = {};           // the hits-and-positions kernels (bsp_count.hip), likewise
     // The edit budget E of the approximate counts (ac_set_max_errors; M1(E): a window adds
     // max(0, E + 1 - d)): 2 = the reference's.  Another one counts on bit-sliced launches only
     // (stage_plan.h budget_refusal); on an ac_create_multi context every shard holds the same value.
@@ -188,7 +192,8 @@ void ensure_warm(ac_ctx* ctx);
 ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hipStream_t stream,
                  bool zero, uint32_t* err = nullptr, int scratch = 0, uint32_t wave_div = 0,
                  const bool* no_n = nullptr, const uint32_t* ulen = nullptr, const StageLaunch* stage = nullptr,
-                 const bool* nrec = nullptr, uint32_t* const* hits = nullptr);
+                 const bool* nrec = nullptr, uint32_t* const* hits = nullptr,
+                 uint32_t* const* pos = nullptr);
 
 // --- capi_comm.cpp
 void comm_destroy(ac_ctx* ctx);  // the context's communicator, if it has one (ac_destroy)

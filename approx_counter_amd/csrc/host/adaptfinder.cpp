@@ -14,6 +14,9 @@
 //   --levels        beside every <out>_<run>.<end> file a <out>_<run>.<end>.levels file: per k-mer, in the
 //                   same order, the sampled windows that hold it within 0, 1, .. E edits (the reference's
 //                   per-level bitfields, approx_counter.cpp:553-565, before their sum; ac_window_hits_samples)
+//   --positions     beside every <out>_<run>.<end> file a <out>_<run>.<end>.positions file: per k-mer, in the
+//                   same order, for every base 1..L of the sampled windows how many of the windows within E
+//                   edits have their best occurrence ending there (ac_window_positions_samples)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -26,6 +29,7 @@
 #include <string>
 #include <vector>
 
+#include "../bs_pos.h"
 #include "../hit_levels.h"
 #include "approx_counter_amd.h"
 #include "host_stages.h"
@@ -85,6 +89,11 @@ const Opt OPTS[] = {
      "k-mer and the number of sampled windows holding it within 0, 1, .. max-errors edits (they sum to its count). "
      "Needs a kmer size of 16 or 18 to 32, a sampling length up to 255, one GPU and reads of at least the sampling "
      "length."},
+    {"", "positions", Kind::Flag,
+     "[MI355X build] also write <out>_<run>.<end>.positions: one line per k-mer of the main file, in its order, the "
+     "k-mer and, for every base 1 to L of the sampled windows, the number of windows holding it within max-errors "
+     "edits whose leftmost best occurrence ends at that base (they sum to the last column of its .levels line). "
+     "Same needs as --levels, with which it can be combined."},
     {"", "host-exact", Kind::Flag,
      "[MI355X build] the reference's host stages: whole reads in memory, exact k-mer count on the CPU"},
     {"", "dump-sample", Kind::String,
@@ -258,6 +267,34 @@ bool export_levels(const pair_vector& ranked, const std::vector<uint64_t>& kmers
     return std::fclose(f) == 0;
 }
 
+// --positions: one line per k-mer of `ranked`, the k-mer and window_len counts -- the position profile of the
+// job's hit and position matrices folded over the distances, by the walk the library's profile kernel runs
+// (bs_pos.h pp_column).
+bool export_positions(const pair_vector& ranked, const std::vector<uint64_t>& kmers, const std::vector<uint32_t>& hits,
+                      const std::vector<uint32_t>& pos, uint32_t n_windows, uint32_t levels, uint32_t window_len, uint32_t k,
+                      const std::string& path) {
+    const uint32_t n = (uint32_t)kmers.size(), words = (n + 31u) / 32u, L = window_len;
+    std::vector<uint32_t> prof((size_t)n * L, 0u);
+    for (uint32_t d = 0; d < levels; ++d)
+        for (uint32_t col = 0; col < words; ++col)
+            acamd::bs::pp_column(hits.data(), pos.data(), n, n_windows, d, col, 0u, n_windows, 1u, [&](uint32_t j, uint32_t p) {
+                if (p < L) ++prof[(size_t)(32u * col + j) * L + p];
+            });
+    std::map<uint64_t, uint32_t> index;  // (the exact count's k-mers are distinct)
+    for (uint32_t c = 0; c < n; ++c) index.emplace(kmers[c], c);
+    std::FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) return false;
+    std::string line;
+    for (const auto& kv : ranked) {
+        const uint32_t c = index.at(kv.first);
+        line = int2dna(kv.first, k);
+        for (uint32_t p = 0; p < L; ++p) line += '\t' + std::to_string(prof[(size_t)c * L + p]);
+        line += '\n';
+        std::fwrite(line.data(), 1, line.size(), f);
+    }
+    return std::fclose(f) == 0;
+}
+
 void open_devices(Devices& dev, uint64_t n_gpus, uint64_t max_errors) {
     if (dev.ctx) return;
     if (n_gpus < 1) n_gpus = 1;
@@ -346,6 +383,7 @@ int main(int argc, char const** argv) {
     skip_end = skip_end || args.val.count("skip_end");
     const bool host_exact = args.val.count("host-exact") > 0;
     const bool levels = args.val.count("levels") > 0;
+    const bool positions = args.val.count("positions") > 0;
     std::string dump_sample;
     get_option(args, "dump-sample", dump_sample);
     const std::string input_file = args.input;
@@ -385,14 +423,16 @@ int main(int argc, char const** argv) {
     // --levels: the hit levels come from the same kernel family under the same constraints
     // (ac_window_hits_samples); what only the sample can tell -- read ends of unequal length -- the
     // library refuses when the count is asked for.
-    if (levels) {
-        const char* why = !(k == 16 || (k >= 18 && k <= 32)) ? "--levels needs a kmer size (-k) of 16 or 18 to 32"
-                          : sl > 255                         ? "--levels needs a sampling length (-sl) of at most 255"
-                          : n_gpus > 1                       ? "--levels needs one GPU (-g 1)"
-                          : host_exact                       ? "--levels cannot be combined with --host-exact"
+    // --positions: the same kernels' sibling family, the same constraints and messages.
+    for (const char* flag : {"--levels", "--positions"}) {
+        if (!(flag[2] == 'l' ? levels : positions)) continue;
+        const char* why = !(k == 16 || (k >= 18 && k <= 32)) ? " needs a kmer size (-k) of 16 or 18 to 32"
+                          : sl > 255                         ? " needs a sampling length (-sl) of at most 255"
+                          : n_gpus > 1                       ? " needs one GPU (-g 1)"
+                          : host_exact                       ? " cannot be combined with --host-exact"
                                                              : nullptr;
         if (why) {
-            std::cerr << error_pref << why << std::endl;
+            std::cerr << error_pref << flag << why << std::endl;
             return 1;
         }
     }
@@ -475,19 +515,28 @@ int main(int argc, char const** argv) {
             // --levels: the hits call in place of the plain count (the same launch yields the counts)
             std::vector<std::vector<uint32_t>> hits(pending.size());
             std::vector<uint32_t*> hits_p(pending.size());
+            // --positions: the positions call, which yields the counts and the levels as well
+            std::vector<std::vector<uint32_t>> pos(pending.size());
+            std::vector<uint32_t*> pos_p(pending.size());
             try {
                 devices();
                 const bool on_device = !host_exact && dev.shards == 1;  // the samples uploaded for the exact count
                 for (size_t e = 0; e < pending.size(); ++e)
                     jobs[e].sample = on_device ? pending[e].dsample : view(pending[e].img);
-                if (levels)
+                if (levels || positions)
                     for (size_t e = 0; e < pending.size(); ++e) {
                         hits[e].assign((size_t)ac_window_hits_words(jobs[e].n_kmers, jobs[e].sample.n_windows,
                                                                     (uint32_t)max_errors) + 1, 0u);
                         hits_p[e] = hits[e].data();
+                        if (positions) {
+                            pos[e].assign((size_t)ac_window_positions_words(jobs[e].n_kmers, jobs[e].sample.n_windows) + 1, 0u);
+                            pos_p[e] = pos[e].data();
+                        }
                     }
                 const ac_status st =
-                    levels      ? ac_window_hits_samples(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size(), hits_p.data())
+                    positions   ? ac_window_positions_samples(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size(),
+                                                              hits_p.data(), pos_p.data())
+                    : levels    ? ac_window_hits_samples(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size(), hits_p.data())
                     : on_device ? ac_error_count_samples(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size())
                                 : ac_error_count_images(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size());
                 if (st != AC_OK) throw std::runtime_error(ac_last_error(dev.ctx));
@@ -510,6 +559,14 @@ int main(int argc, char const** argv) {
                                              (uint32_t)max_errors + 1, (uint32_t)k, path + ".levels")) {
                     std::cerr << error_pref + "Failed to export the hit levels" << std::endl;
                     std::cerr << "Path: " << path + ".levels" << std::endl;
+                    return false;
+                }
+                if (positions &&
+                    !export_positions(sorted_error_count, km[e], hits[e], pos[e], jobs[e].sample.n_windows,
+                                      (uint32_t)max_errors + 1, pending[e].img.length.empty() ? 0u : pending[e].img.length[0],
+                                      (uint32_t)k, path + ".positions")) {
+                    std::cerr << error_pref + "Failed to export the match end positions" << std::endl;
+                    std::cerr << "Path: " << path + ".positions" << std::endl;
                     return false;
                 }
                 if (mr_v > 0) print("Done", tab_level);

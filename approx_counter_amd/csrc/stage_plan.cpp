@@ -58,6 +58,14 @@ const char* hits_refusal(uint32_t max_errors, uint32_t k, uint32_t n, const bool
     return nullptr;
 }
 
+const char* positions_refusal(uint32_t max_errors, uint32_t k, uint32_t n, const bool* live, const uint32_t* ulen,
+                              bool multi_device, const bool* has_pos) {
+    if (const char* why = hits_refusal(max_errors, k, n, live, ulen, multi_device)) return why;
+    for (uint32_t i = 0; i < n; ++i)
+        if (live[i] && !(has_pos && has_pos[i])) return "window positions: pos[i] is NULL for a segment with work";
+    return nullptr;
+}
+
 uint32_t launch_group_size(uint32_t k, bool staged, bool bs) {
     return bs ? BS_GROUP : cands_per_wave(pack_factor(k), staged);
 }

@@ -106,6 +106,11 @@ const char* budget_refusal(uint32_t max_errors, uint32_t k, uint32_t n, const bo
 // the constraint it breaks -- nothing is launched then and nothing falls back.
 const char* hits_refusal(uint32_t max_errors, uint32_t k, uint32_t n, const bool* live, const uint32_t* ulen,
                          bool multi_device);
+// The match end positions' question (ac_window_positions_*; DESIGN.md §4e "Match end positions"): the hit
+// levels' (hits_refusal, asked, not restated), and a position matrix for every segment with work --
+// has_pos[i]: segment i's is not NULL.
+const char* positions_refusal(uint32_t max_errors, uint32_t k, uint32_t n, const bool* live, const uint32_t* ulen,
+                              bool multi_device, const bool* has_pos);
 // Candidates of such a launch's candidate groups: BS_GROUP for a bit-sliced launch, else the
 // word-parallel kernel's candidates per wave.  Everything counted per group goes by it: the work
 // items, the acc slots, the sub-queues, a tagged launch's group error words and their polling.

@@ -166,6 +166,11 @@ struct LaunchArgs {
     // hits[(e * n_windows + w) * ceil(n_kmers / 32) + c / 32] -- read by that kernel family only.
     uint32_t* hits[AC_MAX_SEGS];
     uint32_t want_hits;  // the launch runs a hits-writing kernel (plain bit-sliced launches only)
+    // Match end positions (bsp_count.hip; DESIGN.md §4e "Match end positions"), appended again: per segment
+    // the device matrix of eight bit planes -- bit c % 32 of pos[(b * n_windows + w) * ceil(n_kmers / 32) +
+    // c / 32] is bit b of pos - 1, 0 where window w holds candidate c at no level -- written beside the hits.
+    uint32_t* pos[AC_MAX_SEGS];
+    uint32_t want_pos;  // the launch runs a hits-and-positions kernel (implies want_hits)
 };
 
 inline uint32_t pack_factor(uint32_t k) { return (32u / k) < AC_MAX_PACK ? (32u / k) : AC_MAX_PACK; }
@@ -222,8 +227,30 @@ inline uint64_t bs_rows(uint32_t n_kmers, uint32_t g, uint32_t cpw, uint32_t n_w
     const uint32_t wpr = 64u >> bs_lane_shift(n);
     return ((uint64_t)n_windows + wpr - 1u) / wpr;
 }
+// The hits-and-positions family (bsp_count.hip): eight position planes and per-base hit accumulation more
+// in registers, so the highest residency with no scratch, buffer or global access inside the 4-base block
+// is re-derived per (K, rows) from the compiler's remarks (profiles/r14_bsp_codegen.txt).
+#ifndef BSP_WAVES_PER_SIMD_16
+#define BSP_WAVES_PER_SIMD_16 4  // three rows, k = 16
+#endif
+#ifndef BSP_K_MID
+#define BSP_K_MID 23  // three rows: 3 waves for k = 18..BSP_K_MID, then 2
+#endif
+#ifndef BSP3_K_MID
+#define BSP3_K_MID 18  // four rows: 3 waves up to here, then 2 ...
+#endif
+#ifndef BSP3_K_ONE
+#define BSP3_K_ONE 31  // ... and from here on 1 (two waves spill inside the block even with one base's rows held)
+#endif
+#ifndef BSP3_ONE_BASE_K
+#define BSP3_ONE_BASE_K 26  // four rows: one base's table rows at a time from here on (BS3_ONE_BASE_K's sibling)
+#endif
+constexpr int bsp_waves_per_simd(int k, int max_errors = 2) {
+    return max_errors == 3 ? (k <= BSP3_K_MID ? 3 : k < BSP3_K_ONE ? 2 : 1)
+                           : k <= 16 ? BSP_WAVES_PER_SIMD_16 : k <= BSP_K_MID ? 3 : 2;
+}
 hipError_t resident_waves_bs(uint32_t k, bool staged, int cu_count, uint32_t* waves, uint32_t max_errors = 2,
-                             bool hits = false);
+                             bool hits = false, bool pos = false);
 // bs3_count.hip: the E = 3 kernel for k (AC_BS_K_LIST), plain or staged; nullptr if there is none
 void (*bs3_kernel(uint32_t k, bool staged))(LaunchArgs);
 // bsh_count.hip: the plain hits-writing kernel for k (AC_BS_K_LIST) at edit budget max_errors (0..2: three
@@ -233,6 +260,13 @@ void (*bsh_kernel(uint32_t k, uint32_t max_errors))(LaunchArgs);
 // candidate c (a column popcount); level_counts is zeroed on the stream first
 hipError_t launch_hit_level_counts(const uint32_t* hits, uint32_t n_kmers, uint32_t n_windows, uint32_t levels,
                                    uint32_t* level_counts, hipStream_t stream);
+// bsp_count.hip: the plain hits-and-positions kernel for k at edit budget max_errors; nullptr if there is none
+void (*bsp_kernel(uint32_t k, uint32_t max_errors))(LaunchArgs);
+// bsp_count.hip: profile[(d * n_kmers + c) * window_len + p - 1] = the windows that hold candidate c at
+// distance exactly d with their best occurrence ending at base p (1..window_len), from a hit matrix of
+// `levels` planes and its position matrix; profile is zeroed on the stream first
+hipError_t launch_hit_position_profile(const uint32_t* hits, const uint32_t* pos, uint32_t n_kmers, uint32_t n_windows,
+                                       uint32_t levels, uint32_t window_len, uint32_t* profile, hipStream_t stream);
 
 // Waves of the count kernel for pattern pack P that fit on the device at once.
 hipError_t resident_waves(uint32_t P, bool staged, int cu_count, uint32_t* waves);

@@ -57,6 +57,7 @@
 
 #include "bs_nfa.h"
 #include "bs_nfa_r.h"
+#include "bs_pos.h"
 #include "nrec.h"
 #include "wm_count.h"
 
@@ -659,7 +660,9 @@ namespace {
 // The kernel that counts a launch: word-parallel for pattern pack P (bs_k = 0), or bit-sliced for
 // k = bs_k (AC_BS_K_LIST) -- at an edit budget of 3 one of bs3_count.hip's; nullptr if there is none.
 typedef void (*CountKernel)(LaunchArgs);
-CountKernel count_kernel(uint32_t P, uint32_t bs_k, bool staged, bool eq, uint32_t max_errors = 2u, bool hits = false) {
+CountKernel count_kernel(uint32_t P, uint32_t bs_k, bool staged, bool eq, uint32_t max_errors = 2u, bool hits = false,
+                         bool pos = false) {
+    if (pos) return bs_k && !staged ? bsp_kernel(bs_k, max_errors) : nullptr;
     if (hits) return bs_k && !staged ? bsh_kernel(bs_k, max_errors) : nullptr;
     if (bs_k && max_errors == 3u) return bs3_kernel(bs_k, staged);
     if (bs_k) {
@@ -717,8 +720,9 @@ hipError_t resident_waves(uint32_t P, bool staged, int cu_count, uint32_t* waves
     return occupancy(count_kernel(P, 0u, staged, true), cu_count, waves);
 }
 
-hipError_t resident_waves_bs(uint32_t k, bool staged, int cu_count, uint32_t* waves, uint32_t max_errors, bool hits) {
-    return occupancy(count_kernel(0u, k, staged, true, max_errors, hits), cu_count, waves);
+hipError_t resident_waves_bs(uint32_t k, bool staged, int cu_count, uint32_t* waves, uint32_t max_errors, bool hits,
+                             bool pos) {
+    return occupancy(count_kernel(0u, k, staged, true, max_errors, hits, pos), cu_count, waves);
 }
 
 hipError_t launch_wm2_count(const LaunchArgs& args, hipStream_t stream) {
@@ -731,8 +735,9 @@ hipError_t launch_wm2_count(const LaunchArgs& args, hipStream_t stream) {
     if (args.max_errors > 3u || (args.max_errors != 2u && !args.bs)) return hipErrorInvalidValue;
     // (hits: plain bit-sliced launches only -- there is no other kernel that writes them)
     if (args.want_hits && !(args.bs && !args.staged)) return hipErrorInvalidValue;
+    if (args.want_pos && !args.want_hits) return hipErrorInvalidValue;
     const CountKernel kernel = count_kernel(args.P, args.bs ? args.m : 0u, args.staged != 0u, args.eq != 0u,
-                                            args.max_errors, args.want_hits != 0u);
+                                            args.max_errors, args.want_hits != 0u, args.want_pos != 0u);
     if (!kernel) return hipErrorInvalidValue;
     hipLaunchKernelGGL(kernel, grid, block, 0, stream, args);
     return hipGetLastError();

@@ -499,6 +499,51 @@ ac_status ac_window_hits_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* j
 ac_status ac_hit_level_counts_device(ac_ctx* ctx, const uint32_t* hits, uint32_t n_kmers, uint32_t n_windows,
                                      uint32_t levels, uint32_t* level_counts, void* hip_stream);
 
+/*
+ * Match end positions: where in its window each k-mer's best occurrence ends
+ * (additive exports of ABI 8).  The reference's search delegate is handed every
+ * occurrence (approx_counter.cpp:553-565) and keeps the read and the error
+ * level only; these calls also keep the end.  For a window w of L bases let e(j),
+ * j = 0..L, be the least edit distance of the whole k-mer c against a substring
+ * of w that ends at base j (exclusive; an N matches nothing), d = min over j.
+ * Where d <= E (the context's budget),
+ *     pos(c, w) = min { j : e(j) = d }              1 <= pos <= L
+ * the exclusive end offset of the leftmost occurrence at the best distance.  A
+ * segment's position matrix is eight bit planes of the hit matrix's shape:
+ *     words = ceil(n_kmers / 32)
+ *     pos[(b * n_windows + w) * words + c / 32], bit c % 32
+ *         = bit b of pos(c, w) - 1,   b = 0..7
+ * 0 in every plane where d > E, for candidates >= n_kmers and in windows the
+ * kernel skipped.  Every word is written by the launch: no clearing needed.
+ *   ac_window_positions_words    u32 words of one segment's position matrix:
+ *                                8 * n_windows * ceil(n_kmers / 32)
+ *   ac_window_positions_device   ac_window_hits_device plus one position matrix
+ *                                per segment (pos[i]): counts, hit levels and
+ *                                positions from one launch.
+ *   ac_window_positions_samples  ac_window_hits_samples plus one host position
+ *                                matrix per job (pos_host[j]); synchronous.
+ *   ac_hit_position_profile_device
+ *                                profile[(d * n_kmers + c) * window_len + p - 1]
+ *                                = the windows that hold candidate c at distance
+ *                                exactly d (d < levels, 1..4) with pos = p
+ *                                (1..window_len, 1..256), from a device hit
+ *                                matrix and its position matrix; asynchronous on
+ *                                hip_stream (profile, device memory, is zeroed
+ *                                first).  A position past window_len is dropped.
+ * Where they run, and what is refused: exactly as the hit levels above, plus a
+ * NULL position matrix for a segment that has work (AC_ERR_INVALID before
+ * anything is enqueued).
+ */
+uint64_t ac_window_positions_words(uint32_t n_kmers, uint32_t n_windows);
+ac_status ac_window_positions_device(ac_ctx* ctx, uint32_t k, const ac_segment* segments, uint32_t n_segments,
+                                     const uint32_t* window_len, uint32_t* const* hits, uint32_t* const* pos,
+                                     void* hip_stream);
+ac_status ac_window_positions_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, uint32_t n_jobs,
+                                      uint32_t* const* hits_host, uint32_t* const* pos_host);
+ac_status ac_hit_position_profile_device(ac_ctx* ctx, const uint32_t* hits, const uint32_t* pos, uint32_t n_kmers,
+                                         uint32_t n_windows, uint32_t levels, uint32_t window_len, uint32_t* profile,
+                                         void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,133 @@
+"""The hits-and-positions family of the bit-sliced count kernels (bsp_count.hip: bs_count.inc's body with
+HITS and POS on, over three NFA rows for the edit budgets 0..2 and over four for budget 3; DESIGN.md §4e
+"Match end positions"), from one compile of its translation unit and one of its twin's, bsh_count.hip: the
+assembly, and the compiler's kernel-resource-usage remarks.
+
+Residency: bsp_waves_per_simd(K, E) (wm_count.h) is what __launch_bounds__ and the LDS allocation declare and
+what the host assumes when it sizes a launch; for every listed k and both row counts it equals the occupancy
+the compiler reports.
+
+Op budget, for K = 16, 22 and 32: one copy of the NFA code, the table read in ceil(K / 4) quads per base, no
+scratch, buffer or global access inside the block of 4 bases, and at most 4 (1.5 R + 8) + 8 VALU instructions
+more than the hits-writing twin's block: per base R more for accumulating the hits per base instead of per
+pair (R / 2 before), R for the `new` mask and 8 for the planes -- the straightforward form; the kernel's
+(planes 2-7 once per block) is below it -- plus 8 for wave-uniform index set-up.  The position words are
+ordinary vector stores outside the block, eight beside the R hit words."""
+import os
+import re
+import subprocess
+
+import pytest
+
+from tests.test_bs_nfa_k import LISTED_K
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "approx_counter_amd", "csrc")
+ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
+BASES = 4  # per block (bs_block4)
+ASM_K = [k for k in (16, 22, 32) if k in LISTED_K]
+
+DECLARED_SRC = """
+#include <cstdio>
+#include "bs_nfa.h"
+#include "wm_count.h"
+int main() {
+#define AC_SHOW(KK) std::printf("%d %d %d\\n", KK, acamd::bsp_waves_per_simd(KK, 2), acamd::bsp_waves_per_simd(KK, 3));
+    AC_BS_K_LIST(AC_SHOW)
+    return 0;
+}
+"""
+
+
+def compile_unit(tmp, unit):
+    """(assembly text, {(K, R): occupancy}) of the <unit>_count_kernel instantiations of <unit>_count.hip."""
+    out = str(tmp / f"{unit}_count.s")
+    r = subprocess.run([os.path.join(ROCM, "bin", "hipcc"), "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC",
+                        "-mllvm", "-amdgpu-atomic-optimizer-strategy=None", "-I" + os.path.join(ROOT, "include"),
+                        "-I" + CSRC, "--cuda-device-only", "-S", os.path.join(CSRC, f"{unit}_count.hip"), "-o", out,
+                        "-Rpass-analysis=kernel-resource-usage"], check=True, capture_output=True, text=True)
+    occ, cur = {}, None
+    for line in r.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            k = re.match(rf"_ZN5acamd16{unit}_count_kernelILi(\d+)ELi([34])E", m.group(1))
+            cur = (int(k.group(1)), int(k.group(2))) if k else None
+            continue
+        m = re.search(r"Occupancy \[waves/SIMD\]: (\d+)", line)
+        if m and cur is not None:
+            occ[cur] = int(m.group(1))
+    return open(out).read(), occ
+
+
+@pytest.fixture(scope="module")
+def compiled(tmp_path_factory):
+    return compile_unit(tmp_path_factory.mktemp("asm"), "bsp")
+
+
+@pytest.fixture(scope="module")
+def twin(tmp_path_factory):
+    return compile_unit(tmp_path_factory.mktemp("asm_twin"), "bsh")
+
+
+@pytest.fixture(scope="module")
+def declared(tmp_path_factory):
+    """{(K, R): bsp_waves_per_simd(K, E)} from a host program that includes the kernel's header."""
+    d = tmp_path_factory.mktemp("decl")
+    src, exe = str(d / "declared.cpp"), str(d / "declared")
+    with open(src, "w") as fh:
+        fh.write(DECLARED_SRC)
+    subprocess.run(["g++", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(ROCM, "include"), "-I" + CSRC,
+                    "-I" + os.path.join(ROOT, "include"), src, "-o", exe], check=True)
+    out = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=60).stdout
+    table = {}
+    for ln in out.splitlines():
+        k, r3, r4 = (int(x) for x in ln.split())
+        table[(k, 3)], table[(k, 4)] = r3, r4
+    return table
+
+
+def test_declared_residency_is_the_compilers_occupancy(compiled, declared):
+    _, occ = compiled
+    assert sorted(declared) == sorted((k, r) for k in LISTED_K for r in (3, 4))
+    assert sorted(occ) == sorted(declared)
+    for key in sorted(declared):
+        print(f"K {key[0]} R {key[1]}: declared {declared[key]}, occupancy {occ[key]}")
+        assert occ[key] == declared[key], key
+
+
+def kernel_blocks(text, unit, k, rows):
+    """Basic blocks (lists of mnemonics) of <unit>_count_kernel<k, rows>."""
+    name = f"_ZN5acamd16{unit}_count_kernelILi{k}ELi{rows}E"
+    funcs = [f for f in re.split(r"\n(?=_Z\w+:)", text) if f.startswith(name)]
+    assert len(funcs) == 1
+    body = funcs[0].split(".Lfunc_end")[0]
+    return [[ln.split()[0] for ln in b.split("\n")[1:] if ln.startswith("\t") and not ln.strip().startswith((".", ";"))]
+            for b in re.split(r"\n(?=\.LBB\d+_\d+:)", body)]
+
+
+def count(b, m):
+    return sum(1 for i in b if i.startswith(m))
+
+
+def nfa_block(blocks, k):
+    nfa = [b for b in blocks if count(b, "v_bitop3_b32") >= 4 * k - 8]  # at least a base's rows 1 and 2
+    assert len(nfa) == 1, "one copy of the NFA code"
+    return nfa[0]
+
+
+@pytest.mark.parametrize("rows", [3, 4])
+@pytest.mark.parametrize("k", ASM_K)
+def test_the_nfa_block_with_positions(compiled, twin, k, rows):
+    blocks = kernel_blocks(compiled[0], "bsp", k, rows)
+    b, t = nfa_block(blocks, k), nfa_block(kernel_blocks(twin[0], "bsh", k, rows), k)
+    valu, valu_twin = count(b, "v_"), count(t, "v_")
+    print(f"K {k} R {rows}, per block of {BASES} bases: VALU {valu} (the hits twin's {valu_twin}: +{valu - valu_twin}), "
+          f"v_bitop3_b32 {count(b, 'v_bitop3_b32')}, v_accvgpr {count(b, 'v_accvgpr')}, ds_read_b128 {count(b, 'ds_read_b128')}")
+    assert count(b, "ds_read_b128") == BASES * -(-k // 4)
+    assert not any(i.startswith(("scratch_", "buffer_", "global_")) for i in b)
+    assert valu - valu_twin <= BASES * (1.5 * rows + 8) + 8
+    assert valu > valu_twin  # (the per-base accumulation, the new masks and the planes are in the block)
+    # the hit and position words: vector stores outside the block
+    stores = sum(count(x, "global_store_dword") for x in blocks)
+    print(f"K {k} R {rows}: global_store_dword {stores}")
+    assert stores >= rows + 8

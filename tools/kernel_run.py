@@ -16,6 +16,8 @@ from HIP events around them (back-to-back launches on resident input), for E = 3
 --hits runs the hits-writing kernels (ac_window_hits_device: the same launch also stores every window's hit
 levels, DESIGN.md 4e "Hit levels") and prints the bytes of the matrices beside the time; --level-counts then
 times ac_hit_level_counts_device over the first segment's matrix and prints the rate its bytes were read at.
+--positions runs the hits-and-positions kernels instead (ac_window_positions_device, DESIGN.md 4e "Match end
+positions"); --profile then times ac_hit_position_profile_device over the first segment's two matrices.
 """
 import argparse
 import os
@@ -44,7 +46,12 @@ def main():
     ap.add_argument("--hits", action="store_true", help="the hits-writing kernels (ac_window_hits_device)")
     ap.add_argument("--level-counts", action="store_true",
                     help="with --hits: also time ac_hit_level_counts_device over the first segment's matrix")
+    ap.add_argument("--positions", action="store_true",
+                    help="the hits-and-positions kernels (ac_window_positions_device); implies --hits")
+    ap.add_argument("--profile", action="store_true",
+                    help="with --positions: also time ac_hit_position_profile_device over the first segment's matrices")
     a = ap.parse_args()
+    a.hits = a.hits or a.positions
     import torch
 
     import approx_counter_amd as ac
@@ -79,10 +86,14 @@ def main():
         if a.hits:
             words = [ac.hits_words(s.n_kmers, s.n_windows, a.max_errors) for s in segs]
             hits = [torch.empty(max(w, 1), dtype=torch.int32, device="cuda") for w in words]
+        pos = None
+        if a.positions:
+            pwords = [ac.positions_words(s.n_kmers, s.n_windows) for s in segs]
+            pos = [torch.empty(max(w, 1), dtype=torch.int32, device="cuda") for w in pwords]
         for i in range(a.warmup + a.launches):
             if i == a.warmup:
                 t0.record()
-            c.count_device(args.k, arr, window_len=wlen, hits=hits)
+            c.count_device(args.k, arr, window_len=wlen, hits=hits, positions=pos)
         t1.record()
         torch.cuda.synchronize()
         c.check()
@@ -91,7 +102,8 @@ def main():
         if a.time:
             print(f"k {args.k} max_errors {a.max_errors}: {t0.elapsed_time(t1) / a.launches:.4f} ms per launch "
                   f"({a.launches} launches after {a.warmup})"
-                  + (f"; hits written per launch: {4 * sum(words)} bytes" if a.hits else ""))
+                  + (f"; hits written per launch: {4 * sum(words)} bytes" if a.hits else "")
+                  + (f"; positions written per launch: {4 * sum(pwords)} bytes" if a.positions else ""))
         if a.hits and a.level_counts:
             s0 = segs[0]
             for i in range(a.warmup + a.launches):
@@ -105,6 +117,20 @@ def main():
             print(f"level counts of {4 * words[0]} bytes ({s0.n_kmers} k-mers x {s0.n_windows} windows x "
                   f"{a.max_errors + 1} levels): {ms:.4f} ms per call (memset + kernel), "
                   f"{4 * words[0] / ms / 1e6:.1f} GB/s read")
+        if a.positions and a.profile:
+            s0 = segs[0]
+            for i in range(a.warmup + a.launches):
+                if i == a.warmup:
+                    t0.record()
+                prof = c.hit_position_profile(hits[0], pos[0], s0.n_kmers, s0.n_windows, a.max_errors + 1, wlen[0])
+            t1.record()
+            torch.cuda.synchronize()
+            ms = t0.elapsed_time(t1) / a.launches
+            lc = c.hit_level_counts(hits[0], s0.n_kmers, s0.n_windows, a.max_errors + 1)
+            assert (prof.sum(dim=(0, 2)) == lc[-1]).all(), "the profile does not sum to the last level's counts"
+            print(f"position profile of {4 * (words[0] + pwords[0])} bytes ({s0.n_kmers} k-mers x {s0.n_windows} windows x "
+                  f"{a.max_errors + 1} levels + 8 planes, window_len {wlen[0]}): {ms:.4f} ms per call (memset + kernel), "
+                  f"{4 * (words[0] + pwords[0]) / ms / 1e6:.1f} GB/s of the matrices' bytes")
 
 
 if __name__ == "__main__":
