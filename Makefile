@@ -78,6 +78,15 @@ $(OBJDIR)/bsp_count.o: $(CSRC)/bsp_count.hip $(CSRC)/stage_dev.inc $(CSRC)/count
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) -c $< -o $@
 
+# the staged forms of the two families above (hits from the jobs stage), each a translation unit of its own
+$(OBJDIR)/bshs_count.o: $(CSRC)/bshs_count.hip $(CSRC)/stage_dev.inc $(CSRC)/count_frame.inc $(CSRC)/bs_count.inc $(HDRS)
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) -c $< -o $@
+
+$(OBJDIR)/bsps_count.o: $(CSRC)/bsps_count.hip $(CSRC)/stage_dev.inc $(CSRC)/count_frame.inc $(CSRC)/bs_count.inc $(HDRS)
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) -c $< -o $@
+
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(INCS) -c $< -o $@
@@ -96,7 +105,7 @@ $(HOSTONLY:%=$(OBJDIR)/%.o): $(OBJDIR)/%.o: $(CSRC)/%.cpp $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(CXX) $(HOST_CXXFLAGS) $(HIP_HOST) $(INCS) -c $< -o $@
 
-$(LIB): $(OBJDIR)/wm_count.o $(OBJDIR)/bs3_count.o $(OBJDIR)/bsh_count.o $(OBJDIR)/bsp_count.o $(OBJDIR)/exact_count.o $(OBJDIR)/jobs_stage.o $(CAPI:%=$(OBJDIR)/%.o) $(HOSTONLY:%=$(OBJDIR)/%.o)
+$(LIB): $(OBJDIR)/wm_count.o $(OBJDIR)/bs3_count.o $(OBJDIR)/bsh_count.o $(OBJDIR)/bsp_count.o $(OBJDIR)/bshs_count.o $(OBJDIR)/bsps_count.o $(OBJDIR)/exact_count.o $(OBJDIR)/jobs_stage.o $(CAPI:%=$(OBJDIR)/%.o) $(HOSTONLY:%=$(OBJDIR)/%.o)
 	@mkdir -p $(dir $@)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -pthread
 
@@ -118,6 +127,8 @@ asm: $(WM_SRC) $(HDRS)
 	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) --cuda-device-only -S $(CSRC)/bs3_count.hip -o build/asm/bs3_count.s
 	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) --cuda-device-only -S $(CSRC)/bsh_count.hip -o build/asm/bsh_count.s
 	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) --cuda-device-only -S $(CSRC)/bsp_count.hip -o build/asm/bsp_count.s
+	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) --cuda-device-only -S $(CSRC)/bshs_count.hip -o build/asm/bshs_count.s
+	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) --cuda-device-only -S $(CSRC)/bsps_count.hip -o build/asm/bsps_count.s
 
 clean:
 	rm -rf build $(LIBDIR) $(BINDIR) oracle/_build

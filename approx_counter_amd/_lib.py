@@ -167,6 +167,17 @@ def load():
         L.ac_hit_position_profile_device.argtypes = [vp, p32, p32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                                      ctypes.c_uint32, p32, vp]
         L.ac_hit_position_profile_device.restype = ctypes.c_int
+    if hasattr(L, "ac_window_hits_jobs"):  # (an A/B build of an older library lacks the jobs stage's hits)
+        pp32 = ctypes.POINTER(p32)
+        L.ac_window_hits_jobs.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ACJob), ctypes.c_uint32, pp32]
+        L.ac_window_hits_jobs.restype = ctypes.c_int
+        L.ac_window_positions_jobs.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ACJob), ctypes.c_uint32, pp32, pp32]
+        L.ac_window_positions_jobs.restype = ctypes.c_int
+        L.ac_window_hits_jobs_submit.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ACJob), ctypes.c_uint32, p32, pp32, vp]
+        L.ac_window_hits_jobs_submit.restype = ctypes.c_int
+        L.ac_window_positions_jobs_submit.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ACJob), ctypes.c_uint32, p32, pp32,
+                                                      pp32, vp]
+        L.ac_window_positions_jobs_submit.restype = ctypes.c_int
     L.ac_exact_path.argtypes = [vp]
     L.ac_exact_path.restype = ctypes.c_int
     pint = ctypes.POINTER(ctypes.c_int)

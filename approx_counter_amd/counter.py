@@ -414,14 +414,65 @@ class ApproxCounter:
         check(st, self._h)
         return jobs.results()
 
-    def submit_jobs(self, k: int, jobs: "Jobs", d_counts, stream=None) -> None:
+    def submit_jobs(self, k: int, jobs: "Jobs", d_counts, stream=None, hits=None, positions=None) -> None:
         """ac_error_count_jobs_submit: pack + send + launch; uint32 counts (jobs concatenated)
-        go to the device tensor `d_counts` on `stream` (asynchronous)."""
+        go to the device tensor `d_counts` on `stream` (asynchronous).
+        hits: one device tensor per job (None for a job without work), of hits_words(...) int32 / uint32 each
+        -- ac_window_hits_jobs_submit, the same launch also stores every window's hit levels there; positions:
+        beside it one tensor of positions_words(...) per job (ac_window_positions_jobs_submit)."""
         ptr = ctypes.cast(ctypes.c_void_p(d_counts.data_ptr()), ctypes.POINTER(ctypes.c_uint32))
-        st = self._L.ac_error_count_jobs_submit(self._h, int(k), jobs.array, len(jobs.array), ptr,
-                                                ctypes.c_void_p(stream or 0))
+        if hits is None and positions is None:
+            st = self._L.ac_error_count_jobs_submit(self._h, int(k), jobs.array, len(jobs.array), ptr,
+                                                    ctypes.c_void_p(stream or 0))
+            if st:
+                check(st, self._h)
+            return
+        if not hasattr(self._L, "ac_window_hits_jobs_submit"):
+            raise _lib.ApproxCounterError(_lib.AC_ERR_INVALID, "this build of the library has no ac_window_hits_jobs_submit")
+        if hits is None:
+            raise ValueError("positions come with the hits: pass hits too")
+        dev = lambda ts: (_lib.p32 * len(jobs.array))(*[  # noqa: E731
+            ctypes.cast(ctypes.c_void_p(t.data_ptr() if t is not None else None), _lib.p32) for t in ts])
+        if positions is None:
+            st = self._L.ac_window_hits_jobs_submit(self._h, int(k), jobs.array, len(jobs.array), ptr, dev(hits),
+                                                    ctypes.c_void_p(stream or 0))
+        else:
+            st = self._L.ac_window_positions_jobs_submit(self._h, int(k), jobs.array, len(jobs.array), ptr, dev(hits),
+                                                         dev(positions), ctypes.c_void_p(stream or 0))
         if st:
             check(st, self._h)
+
+    def window_hits_jobs(self, k: int, jobs, positions: bool = False) -> list:
+        """ac_window_hits_jobs: count_jobs -- the whole stage from Dna5 host buffers, `jobs` a Jobs object or a
+        sequence of (kmers, Dna5Sample / windows); pinned Dna5Samples are packed by the kernel -- whose one
+        launch also writes every window's hit levels; returns one WindowHits per job, row w = the job's window
+        w.  Only where the bit-sliced kernel counts (k = 16 or 18..32, every job with work holding equal
+        windows of 1..256 bases, a single-device context), at the context's edit budget; anything else raises
+        (AC_ERR_INVALID).  positions: ac_window_positions_jobs -- every WindowHits also holds the match end
+        positions (.end_positions(), .position_profile())."""
+        if not hasattr(self._L, "ac_window_hits_jobs"):
+            raise _lib.ApproxCounterError(_lib.AC_ERR_INVALID, "this build of the library has no ac_window_hits_jobs")
+        if not isinstance(jobs, Jobs):
+            jobs = Jobs([(km, w if isinstance(w, Dna5Sample) else Dna5Sample.from_windows(w)) for km, w in jobs])
+        E = self.max_errors
+        shapes = [(int(km.size), smp.n_windows, int(smp.length[0]) if smp.n_windows else 0)
+                  for km, smp in zip(jobs.kmers, jobs.samples)]
+        # (all ones: the call writes every word, so one it missed would show as a row of hits, not pass as none)
+        mats = [np.full(max(hits_words(nk, nw, E), 1), 0xFFFFFFFF, dtype=np.uint32) for nk, nw, _ in shapes]
+        # (a job without work has no matrix: NULL)
+        host = lambda ms: (_lib.p32 * len(ms))(*[  # noqa: E731
+            _ptr(m, ctypes.c_uint32) if nk and nw else None for m, (nk, nw, _) in zip(ms, shapes)])
+        hp = host(mats)
+        if positions:
+            planes = [np.full(max(positions_words(nk, nw), 1), 0xFFFFFFFF, dtype=np.uint32) for nk, nw, _ in shapes]
+            pp = host(planes)
+            check(self._L.ac_window_positions_jobs(self._h, int(k), jobs.array, len(jobs.array), hp, pp), self._h)
+            return [WindowHits(c, m[: hits_words(nk, nw, E)].reshape(E + 1, nw, (nk + 31) // 32), nk,
+                               p[: positions_words(nk, nw)].reshape(8, nw, (nk + 31) // 32), L, self)
+                    for c, m, p, (nk, nw, L) in zip(jobs.results(), mats, planes, shapes)]
+        check(self._L.ac_window_hits_jobs(self._h, int(k), jobs.array, len(jobs.array), hp), self._h)
+        return [WindowHits(c, m[: hits_words(nk, nw, E)].reshape(E + 1, nw, (nk + 31) // 32), nk)
+                for c, m, (nk, nw, _) in zip(jobs.results(), mats, shapes)]
 
     def _sample_jobs(self, fn, k, parts):
         keep, arr = [], []
@@ -722,3 +773,20 @@ def error_count(sequences, exact_count, nb_thread: int = 4, k: int = 16, v: int 
     # the sample as a StringSet<Dna5String>: packed, sent and counted by ac_error_count_jobs
     counts = ctr.count_jobs(k, [(np.array(kmers, dtype=np.uint64), Dna5Sample.from_windows(sequences))])[0]
     return {km: int(c) for km, c in zip(kmers, counts)}
+
+
+def error_levels(sequences, exact_count, nb_thread: int = 4, k: int = 16, v: int = 0, max_errors: int = 2) -> dict:
+    """errorCount's bitfields (approx_counter.cpp:553-565), which the reference sums away: {kmer: (n_0, .., n_E)},
+    n_e = the sequences that hold the k-mer within e edits, E = max_errors.  sum(levels) is error_count's value.
+    Through ApproxCounter.window_hits_jobs, so only where that runs: k = 16 or 18..32, sequences of one length
+    of 1..256 bases."""
+    del nb_thread, v  # OpenMP thread count / verbosity of the CPU reference
+    kmers = [int(km) for km, _ in exact_count]
+    if not kmers:
+        return {}
+    ctr = _counter()
+    if ctr.max_errors != max_errors:
+        ctr.set_max_errors(max_errors)
+    wh = ctr.window_hits_jobs(k, [(np.array(kmers, dtype=np.uint64), Dna5Sample.from_windows(sequences))])[0]
+    lv = wh.level_counts()
+    return {km: tuple(int(x) for x in lv[:, i]) for i, km in enumerate(kmers)}

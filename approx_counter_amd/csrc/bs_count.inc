@@ -1,7 +1,8 @@
 // bs_count.inc -- the bit-sliced count kernel's body (DESIGN.md §4e), included by wm_count.hip (three NFA
 // rows: edit budgets 0..2), by bs3_count.hip (four rows: budget 3), by bsh_count.hip (either, and the
-// windows' hit words stored beside the counts) and by bsp_count.hip (either, the hit words and the match end
-// positions) inside their anonymous namespaces:
+// windows' hit words stored beside the counts), by bsp_count.hip (either, the hit words and the match end
+// positions) and by bshs_count.hip / bsps_count.hip (the staged forms of those two) inside their anonymous
+// namespaces:
 // the NFA's place in the frame of count_frame.inc (deal, staged prologue,
 // sub-queues, gate, count hand-off -- the word-parallel kernel's), with another mapping of a wave
 // onto the work.
@@ -172,15 +173,15 @@ struct BsState<K, R, true> {
 
 // R = 3: the edit budget E = a.max_errors is 0, 1 or 2 (a smaller budget drops levels where a row's
 // hit masks become counts); R = 4: E = 3.
-// HITS (bsh_count.hip, plain launches; DESIGN.md §4e "Hit levels"): where a row's masks become counts,
+// HITS (bsh_count.hip: plain launches, bshs_count.hip: staged ones; DESIGN.md §4e "Hit levels", "Hits from the
+// jobs stage"): where a row's masks become counts,
 // every lane whose window and candidate block exist also stores its hit word of each level 0..E to the
 // segment's matrix a.hits[si] -- one word, one lane, one row: no memset, no atomic.
-// POS (bsp_count.hip, implies HITS; DESIGN.md §4e "Match end positions"): the same lanes also store the
+// POS (bsp_count.hip / bsps_count.hip, implies HITS; DESIGN.md §4e "Match end positions"): the same lanes also store the
 // eight plane words of their candidates' end positions to a.pos[si], masked to the pairs with a hit.
 template <int K, bool STAGED, int R = 3, bool HITS = false, bool POS = false>
 __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
     static_assert(K >= 3 && K <= 32, "a k-mer is one 64-bit word (dna2int layout: K = 32 fills it)");
-    static_assert(!(HITS && STAGED), "the staged instantiations do not write hits");
     static_assert(HITS || !POS, "positions come with the hits");
     constexpr uint32_t CS = BsLds<K>::CHAR_STRIDE;
     const uint32_t lane = threadIdx.x & 63u;
@@ -478,7 +479,9 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
                 const uint32_t keep = live & (left >= 32u ? ~0u : (1u << left) - 1u);
                 const uint64_t words = (uint64_t)((sg.n_kmers + 31u) >> 5);
                 uint32_t* hp = a.hits[si] + (uint64_t)(row * wpr + wl) * words + (BS_GROUP / 32u) * g + blk;
-                const uint64_t plane = (uint64_t)seg_nw * words;
+                // (the planes lie the matrix's window count apart: the segment's own, unless the launch counts a
+                // window sub-range of a job into the job's matrix -- a part of a DMA-path jobs call)
+                const uint64_t plane = (uint64_t)a.mat_nw[si] * words;
                 if constexpr (R == 3) {
                     hp[0] = ~s.a0 & keep;
                     if (budget >= 1u) hp[plane] = ~s.a1 & keep;

@@ -2,7 +2,7 @@
 // bs_count.inc's body with HITS on, which beside the counts stores every window's hit word of each level
 // 0..E -- what the reference keeps per read in tcount[errors][read] (approx_counter.cpp:553-565) before
 // vectorSum collapses it (580-596).  One instantiation per k in AC_BS_K_LIST over three NFA rows (edit
-// budgets 0..2) and over four (budget 3), plain only: the jobs stage's staged launches write no hits.  A
+// budgets 0..2) and over four (budget 3), plain only: the staged forms are bshs_count.hip's.  A
 // translation unit of its own, like bs3_count.hip, so that the counting kernels' device compiles stay
 // what they were; wm_count.hip's dispatch (count_kernel) takes its kernels from bsh_kernel().
 // With it: the kernel that turns a hit matrix into per-level counts (hit_levels.h).

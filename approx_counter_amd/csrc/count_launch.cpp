@@ -51,11 +51,13 @@ void ensure_warm(ac_ctx* ctx) {
 // That was measured at four waves per SIMD and holds for the kernels of that residency (k = 16) only:
 // the wider patterns' kernels, at 2-3 waves per SIMD, launch every resident workgroup.
 // AC_BS_WAVES_PCT (1..100) sets the share for every bit-sliced launch instead, for A/B runs.
-static uint64_t bs_launch_waves(uint32_t k, uint32_t max_errors, bool hits, bool pos, uint64_t items, uint64_t resident) {
+static uint64_t bs_launch_waves(uint32_t k, uint32_t max_errors, bool hits, bool pos, bool staged, uint64_t items,
+                                uint64_t resident) {
     static const int pct = env_int("AC_BS_WAVES_PCT", 0);
     const int e = max_errors == 3u ? 3 : 2;
-    const int per_simd = pos    ? acamd::bsp_waves_per_simd((int)k, e)
-                         : hits ? acamd::bsh_waves_per_simd((int)k, e) : acamd::bs_waves_per_simd((int)k, e);
+    const int per_simd = pos    ? (staged ? acamd::bsps_waves_per_simd((int)k, e) : acamd::bsp_waves_per_simd((int)k, e))
+                         : hits ? (staged ? acamd::bshs_waves_per_simd((int)k, e) : acamd::bsh_waves_per_simd((int)k, e))
+                                : acamd::bs_waves_per_simd((int)k, e);
     const bool three_of_four = per_simd == 4 && items > resident &&
                                4 * items <= 5 * resident;
     const uint64_t want = pct > 0 ? resident * (uint64_t)std::min(pct, 100) / 100
@@ -75,14 +77,18 @@ static uint64_t bs_launch_waves(uint32_t k, uint32_t max_errors, bool hits, bool
 // Staged launch (the early-launch stage): the kernel copies each
 // segment's region from src (the pinned block) to dst once the host flags it in
 // host_hdr, and reports its completion there.
-// `hits` (optional; plain launches that store their counts): per segment the device matrix the launch
-// also writes its windows' hit words to (DESIGN.md §4e "Hit levels"); refused -- hits_refusal -- unless
-// the launch is bit-sliced.
+// `hits` (optional): per segment the device matrix the launch also writes its windows' hit words to
+// (DESIGN.md §4e "Hit levels"); refused -- hits_refusal -- unless the launch is bit-sliced.  A staged launch
+// takes the staged hits kernels (the jobs stage, DESIGN.md §4e "Hits from the jobs stage").
 // `pos` (optional, with `hits`): per segment the device matrix of end-position planes the launch writes as
 // well (DESIGN.md §4e "Match end positions"), by the hits-and-positions kernels.
+// `mat_windows` (optional, with `hits`): per segment the window count of the matrix hits[i] / pos[i] point
+// into, when the segment is a window sub-range [lo, hi) of it (the caller has folded row lo into the
+// pointers); NULL: every segment fills its whole matrix.
 ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hipStream_t stream, bool zero,
                  uint32_t* err, int scratch, uint32_t wave_div, const bool* no_n, const uint32_t* ulen,
-                 const StageLaunch* stage, const bool* nrec, uint32_t* const* hits, uint32_t* const* pos) {
+                 const StageLaunch* stage, const bool* nrec, uint32_t* const* hits, uint32_t* const* pos,
+                 const uint32_t* mat_windows) {
     ensure_warm(ctx);
     ac_ctx::Scratch& sc = ctx->sc[scratch];
     if (ac_status st = check_k(ctx, k)) return st;
@@ -112,7 +118,9 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
         if (const char* why = pos ? acamd::positions_refusal(E, k, n, live, ulen, !ctx->peers.empty(), has_pos)
                                   : acamd::hits_refusal(E, k, n, live, ulen, !ctx->peers.empty()))
             return fail(ctx, AC_ERR_INVALID, why);
-        if (staged || !zero) return fail(ctx, AC_ERR_INVALID, "window hits need a plain launch that stores its counts");
+        for (uint32_t i = 0; i < n; ++i)
+            if (mat_windows && live[i] && mat_windows[i] < segs[i].sample.n_windows)
+                return fail(ctx, AC_ERR_INVALID, "window hits: a segment has more windows than its matrix");
         for (uint32_t i = 0; i < n; ++i)
             if (live[i] && !hits[i]) return fail(ctx, AC_ERR_INVALID, "window hits: hits[i] is NULL for a segment with work");
         for (uint32_t i = 0; i < n; ++i)
@@ -158,8 +166,8 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
     // of AC_WAVES_PER_BLOCK waves are dealt round-robin over blocks of that many
     // consecutive sub-queues (one candidate group each).
     uint32_t& res_p = !bs    ? ctx->resident[staged][P]
-                      : pos  ? ctx->resident_bsp[E == 3u][k]
-                      : hits ? ctx->resident_bsh[E == 3u][k]
+                      : pos  ? (staged ? ctx->resident_bsps : ctx->resident_bsp)[E == 3u][k]
+                      : hits ? (staged ? ctx->resident_bshs : ctx->resident_bsh)[E == 3u][k]
                              : E == 3u ? ctx->resident_bs3[staged][k] : ctx->resident_bs[staged][k];
     if (!res_p)
         AC_HIP(ctx, bs ? acamd::resident_waves_bs(k, staged, ctx->cu_count, &res_p, E == 3u ? 3u : 2u, hits != nullptr,
@@ -168,7 +176,7 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
     const uint64_t fit = wave_div > 1 ? std::max<uint64_t>(AC_WAVES_PER_BLOCK, res_p / wave_div / AC_WAVES_PER_BLOCK *
                                                                                    AC_WAVES_PER_BLOCK)
                                       : res_p;
-    const uint64_t resident = bs ? bs_launch_waves(k, E, hits != nullptr, pos != nullptr, items, fit) : fit;
+    const uint64_t resident = bs ? bs_launch_waves(k, E, hits != nullptr, pos != nullptr, staged, items, fit) : fit;
     const uint32_t wpw = (uint32_t)std::max<uint64_t>(1, (items + resident - 1) / resident);
 #ifdef AC_FORCE_CHUNK  // A/B builds (tools/variants.sh): fixed item size
     const uint32_t chunk = AC_FORCE_CHUNK;
@@ -319,6 +327,7 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
     if (hits) {
         a.want_hits = 1u;
         for (uint32_t i = 0; i < n; ++i) a.hits[i] = a.seg[i].queue_begin != ~0u ? hits[i] : nullptr;
+        for (uint32_t i = 0; i < n; ++i) a.mat_nw[i] = mat_windows ? mat_windows[i] : a.seg[i].n_windows;
     }
     if (pos) {
         a.want_pos = 1u;

@@ -28,10 +28,10 @@ struct ac_ctx {
     void* d_buf[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     size_t d_cap[6] = {0, 0, 0, 0, 0, 0};
     std::vector<uint32_t> h_counts;
-    // ac_window_hits_samples: the jobs' device hit matrices, one block (grow-only)
+    // ac_window_hits_samples / ac_window_hits_jobs: the jobs' device hit matrices, one block (grow-only)
     void* d_hits = nullptr;
     size_t d_hits_cap = 0;
-    // ac_window_positions_samples: the jobs' device position matrices, likewise
+    // ac_window_positions_samples / ac_window_positions_jobs: the jobs' device position matrices, likewise
     void* d_pos = nullptr;
     size_t d_pos_cap = 0;
     // ac_error_count staging: the inputs packed back to back in pinned host
@@ -91,6 +91,8 @@ struct ac_ctx {
                                                  // at its first launch
     uint32_t resident_bsh[2][33] = {};           // the hits-writing kernels (bsh_count.hip): [E == 3][k]
     uint32_t resident_bsp[2][33] = {};           // the hits-and-positions kernels (bsp_count.hip), likewise
+    uint32_t resident_bshs[2][33] = {};          // their staged forms (bshs_count.hip, bsps_count.hip), likewise
+    uint32_t resident_bsps[2][33] = {};
     // The edit budget E of the approximate counts (ac_set_max_errors; M1(E): a window adds
     // max(0, E + 1 - d)): 2 = the reference's.  Another one counts on bit-sliced launches only
     // (stage_plan.h budget_refusal); on an ac_create_multi context every shard holds the same value.
@@ -193,7 +195,7 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
                  bool zero, uint32_t* err = nullptr, int scratch = 0, uint32_t wave_div = 0,
                  const bool* no_n = nullptr, const uint32_t* ulen = nullptr, const StageLaunch* stage = nullptr,
                  const bool* nrec = nullptr, uint32_t* const* hits = nullptr,
-                 uint32_t* const* pos = nullptr);
+                 uint32_t* const* pos = nullptr, const uint32_t* mat_windows = nullptr);
 
 // --- capi_comm.cpp
 void comm_destroy(ac_ctx* ctx);  // the context's communicator, if it has one (ac_destroy)

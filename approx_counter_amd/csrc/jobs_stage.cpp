@@ -252,6 +252,24 @@ struct StageCall {
     int part;
     uint32_t wave_div;
     bool zero;
+    // hits from the jobs stage: the jobs' whole device matrices (NULL: a plain count), of which this launch
+    // writes the rows of its window ranges (JobPlan::mat_row_off)
+    uint32_t* const* hits;
+    uint32_t* const* pos;
+};
+
+// The launch's rows of the jobs' matrices: the first row of the launch's window range folded into the
+// pointers (a job without work here keeps none), for launch()'s hits / pos / mat_windows.
+struct PartMats {
+    uint32_t* hits[AC_MAX_JOBS] = {};
+    uint32_t* pos[AC_MAX_JOBS] = {};
+    PartMats(const StageCall& c) {
+        for (uint32_t j = 0; j < c.p.n; ++j) {
+            const bool work = c.jobs[j].n_kmers && c.p.hi[j] > c.p.lo[j];
+            if (work && c.hits && c.hits[j]) hits[j] = c.hits[j] + c.p.mat_row_off[j];
+            if (work && c.pos && c.pos[j]) pos[j] = c.pos[j] + c.p.mat_row_off[j];
+        }
+    }
 };
 
 // Device packing: device-visible addresses of the device-packed jobs' Dna5 bytes and
@@ -451,7 +469,9 @@ struct EarlyRun {
     ac_status go() {
         ac_segment segs[AC_MAX_JOBS];
         make_segs(c.jobs, p, m, c.d_counts, segs);
-        if (ac_status st = launch(c.ctx, c.k, segs, p.n, c.stream, c.zero, nullptr, p.scratch, 0, no_n, p.ulen, &stg, p.nrec))
+        const PartMats mats(c);
+        if (ac_status st = launch(c.ctx, c.k, segs, p.n, c.stream, c.zero, nullptr, p.scratch, 0, no_n, p.ulen, &stg, p.nrec,
+                                  c.hits ? mats.hits : nullptr, c.hits && c.pos ? mats.pos : nullptr, p.mat_windows))
             return st;
         clk.mark(PH_LAUNCH_ENQ);
         launched = true;
@@ -688,8 +708,10 @@ ac_status run_dma(const StageCall& c, const std::vector<Task>& tasks, const Slot
     make_segs(c.jobs, p, m, c.d_counts, segs);
     // the synchronous path reads the error word back with the counts; a
     // submit reports through the context's word (ac_check)
+    const PartMats mats(c);
     if (ac_status st = launch(ctx, c.k, segs, p.n, c.stream, c.zero, c.d_counts ? nullptr : (uint32_t*)(m.hd + p.off_err),
-                              p.scratch, c.wave_div, no_n, p.ulen, nullptr, p.nrec))
+                              p.scratch, c.wave_div, no_n, p.ulen, nullptr, p.nrec, c.hits ? mats.hits : nullptr,
+                              c.hits && c.pos ? mats.pos : nullptr, p.mat_windows))
         return st;
     clk.mark(PH_LAUNCH_ENQ);
     clk.mark(PH_D2H_ENQ);
@@ -711,11 +733,18 @@ void run_on_pool(uint32_t n, const std::function<void(uint32_t)>& fn) { acamd::h
 // Staging slots: a synchronous call's part q uses slot q (a one-part early
 // launch alternates between slots 0 and 1); submits alternate between two
 // sets of slots of their own.
+// `hits` / `pos` (optional): the jobs' whole device matrices; the launch also writes the hit levels (and the
+// end positions) of its window ranges into their rows (DESIGN.md §4e "Hits from the jobs stage").
 ac_status stage_and_launch(ac_ctx* ctx, uint32_t k, const ac_job* jobs, JobPlan& p, hipStream_t stream,
-                           uint32_t* d_counts, int part = 0, uint32_t wave_div = 0, bool zero = true) {
+                           uint32_t* d_counts, int part = 0, uint32_t wave_div = 0, bool zero = true,
+                           uint32_t* const* hits = nullptr, uint32_t* const* pos = nullptr) {
     PhaseClock clk;
     const uint32_t hooks = g_test_hooks.load(std::memory_order_relaxed);
     p.max_errors = ctx->max_errors;
+    p.want_hits = hits != nullptr;
+    p.want_pos = hits && pos;
+    p.multi_device = !ctx->peers.empty();
+    for (uint32_t j = 0; j < p.n; ++j) p.has_pos[j] = pos && pos[j];
     std::vector<Task> tasks = acamd::plan_stage(k, jobs, p, d_counts != nullptr, acamd::host_pool().size(), task_windows(),
                                                 stage_early(), hooks, run_on_pool);
     clk.mark(PH_SPAN);
@@ -732,7 +761,7 @@ ac_status stage_and_launch(ac_ctx* ctx, uint32_t k, const ac_job* jobs, JobPlan&
     if (ac_status st = acquire_slot(ctx, jobs, p, &m)) return st;
     clk.mark(PH_LAYOUT);
     Packer pack(jobs, p, tasks, m.h);
-    const StageCall c{ctx, k, jobs, p, stream, d_counts, part, wave_div, zero};
+    const StageCall c{ctx, k, jobs, p, stream, d_counts, part, wave_div, zero, hits, pos};
     return p.early ? run_early(c, tasks, dp, m, pack, clk, hooks) : run_dma(c, tasks, m, pack, clk);
 }
 
@@ -753,6 +782,9 @@ CallShape call_shape(const ac_job* jobs, uint32_t n_jobs, bool allow_early) {
     CallShape s;
     s.early = allow_early && stage_early() && live_work(jobs, n_jobs);
     s.parts = (!s.early && total_w >= 2048) ? acamd::stage_parts(total_w) : 1;
+    // (test-only hook: two parts whatever the size)
+    if (!s.early && live_work(jobs, n_jobs))
+        s.parts = std::max(s.parts, acamd::stage_parts(0, g_test_hooks.load(std::memory_order_relaxed)));
     s.cuts = acamd::part_cuts(jobs, n_jobs, s.parts);
     return s;
 }
@@ -853,8 +885,19 @@ void add_counts(const Unit& u, const ac_job* jobs, uint32_t n_jobs) {
 
 // The synchronous jobs stage (ac_error_count_jobs).  allow_early = false: the DMA path whatever
 // AC_STAGE_EARLY says.  *stage_timeout: the early launch gave up waiting for the host's inputs.
+// `mats` (optional): the call also returns hit levels (and end positions) -- every unit's launch writes its
+// rows of the context's device matrices, which the last unit's stream copies to the caller's host matrices
+// once every unit has been collected; the call returns when those copies have landed.
+struct HostMats {
+    uint32_t* const* hits_host;
+    uint32_t* const* pos_host;  // NULL: hit levels only
+    uint32_t* d_hits[AC_MAX_JOBS] = {};
+    uint32_t* d_pos[AC_MAX_JOBS] = {};
+    size_t hits_bytes[AC_MAX_JOBS] = {}, pos_bytes[AC_MAX_JOBS] = {};
+};
+
 ac_status count_jobs_sync(ac_ctx* ctx, uint32_t k, const ac_job* jobs, uint32_t n_jobs, bool allow_early,
-                          bool* stage_timeout) {
+                          bool* stage_timeout, const HostMats* mats = nullptr) {
     *stage_timeout = false;
     std::vector<Unit> units;
     if (ac_status st = make_units(ctx, jobs, n_jobs, allow_early, units)) return st;
@@ -863,7 +906,8 @@ ac_status count_jobs_sync(ac_ctx* ctx, uint32_t k, const ac_job* jobs, uint32_t 
     for (size_t g = 0; g < units.size(); ++g) {
         Unit& u = units[g];
         AC_HIP(u.c, hipSetDevice(u.c->device));
-        if (ac_status st = stage_and_launch(u.c, k, jobs, u.plan, u.stream, nullptr, u.part, u.wave_div))
+        if (ac_status st = stage_and_launch(u.c, k, jobs, u.plan, u.stream, nullptr, u.part, u.wave_div, true,
+                                            mats ? mats->d_hits : nullptr, mats && mats->pos_host ? mats->d_pos : nullptr))
             return u.c != ctx ? fail(ctx, st, "shard " + std::to_string(g) + ": " + u.c->err) : st;
     }
     for (uint32_t j = 0; j < n_jobs; ++j)
@@ -885,6 +929,18 @@ ac_status count_jobs_sync(ac_ctx* ctx, uint32_t k, const ac_job* jobs, uint32_t 
         add_counts(u, jobs, n_jobs);
     }
     if (first_err == AC_OK) units[0].c->last_mode = stage_mode_of(units[0].plan);
+    if (first_err == AC_OK && mats) {
+        // Every unit's counts are in, so every DMA-path unit's stream has been waited for; a tagged early
+        // launch's counts may arrive before its kernel has retired, and the copies follow it on its stream.
+        hipStream_t st = units.back().stream;
+        for (uint32_t j = 0; j < n_jobs; ++j) {
+            if (!jobs[j].n_kmers || !jobs[j].sample.n_windows) continue;
+            AC_HIP(ctx, hipMemcpyAsync(mats->hits_host[j], mats->d_hits[j], mats->hits_bytes[j], hipMemcpyDeviceToHost, st));
+            if (mats->pos_host)
+                AC_HIP(ctx, hipMemcpyAsync(mats->pos_host[j], mats->d_pos[j], mats->pos_bytes[j], hipMemcpyDeviceToHost, st));
+        }
+        AC_HIP(ctx, hipStreamSynchronize(st));
+    }
     if (g_trace.on) {
         clk.mark(PH_WIDEN);
         ++g_trace.calls;
@@ -894,25 +950,128 @@ ac_status count_jobs_sync(ac_ctx* ctx, uint32_t k, const ac_job* jobs, uint32_t 
     return first_err;
 }
 
-}  // namespace
+// The hit levels' question (hits_refusal / positions_refusal), asked of the whole call over every job's
+// whole sample before anything is packed or enqueued, like check_jobs asks the budget's: a call may become
+// several launches (parts), each of which asks again of its own plan, and a call whose whole samples hold
+// equal windows has parts that do.  `hits` / `pos`: the caller's matrices, host or device, one per job (a
+// job without work may pass NULL); with_pos: positions are asked for too.
+ac_status check_jobs_hits(ac_ctx* ctx, uint32_t k, const ac_job* jobs, uint32_t n_jobs, uint32_t* const* hits,
+                          bool with_pos, uint32_t* const* pos) {
+    if (n_jobs && !hits) return fail(ctx, AC_ERR_INVALID, "window hits: hits is NULL");
+    if (with_pos && n_jobs && !pos) return fail(ctx, AC_ERR_INVALID, "window positions: pos is NULL");
+    bool live[AC_MAX_JOBS], has_pos[AC_MAX_JOBS];
+    uint32_t ulen[AC_MAX_JOBS];
+    for (uint32_t j = 0; j < n_jobs; ++j) {
+        const ac_dna5_windows& s = jobs[j].sample;
+        live[j] = jobs[j].n_kmers && s.n_windows;
+        has_pos[j] = with_pos && pos[j];
+        ulen[j] = s.n_windows ? s.length[0] : AC_NO_ULEN;
+        for (uint32_t i = 1; i < s.n_windows && ulen[j] != AC_NO_ULEN; ++i)
+            if (s.length[i] != ulen[j]) ulen[j] = AC_NO_ULEN;
+    }
+    if (const char* why = with_pos ? acamd::positions_refusal(ctx->max_errors, k, n_jobs, live, ulen, !ctx->peers.empty(), has_pos)
+                                   : acamd::hits_refusal(ctx->max_errors, k, n_jobs, live, ulen, !ctx->peers.empty()))
+        return fail(ctx, AC_ERR_INVALID, why);
+    for (uint32_t j = 0; j < n_jobs; ++j)
+        if (live[j] && !hits[j]) return fail(ctx, AC_ERR_INVALID, "window hits: hits[j] is NULL for a job with work");
+    return AC_OK;
+}
 
-extern "C" {
-
-ac_status ac_error_count_jobs(ac_ctx* ctx, uint32_t k, const ac_job* jobs, uint32_t n_jobs) {
+// ac_error_count_jobs, and -- hits_host: one host matrix per job -- ac_window_hits_jobs, and -- pos_host
+// beside it -- ac_window_positions_jobs.
+ac_status count_jobs(ac_ctx* ctx, uint32_t k, const ac_job* jobs, uint32_t n_jobs, uint32_t* const* hits_host,
+                     bool with_pos, uint32_t* const* pos_host) {
     if (ac_status st = check_jobs(ctx, k, jobs, n_jobs)) return st;
     for (uint32_t j = 0; j < n_jobs; ++j)
         if (jobs[j].n_kmers && !jobs[j].counts) return fail(ctx, AC_ERR_INVALID, "job counts is NULL");
     if (n_jobs == 0) return AC_OK;
+    HostMats mats{hits_host, with_pos ? pos_host : nullptr};
+    const bool want_hits = hits_host != nullptr;
+    if (want_hits) {
+        if (ac_status st = check_jobs_hits(ctx, k, jobs, n_jobs, hits_host, with_pos, pos_host)) return st;
+        // The context's device matrices, back to back in one block each, grown here: before any launch is
+        // enqueued, so that no early launch -- which waits for this thread's packing -- waits on an allocation.
+        size_t all = 0, all_pos = 0;
+        for (uint32_t j = 0; j < n_jobs; ++j) {
+            mats.hits_bytes[j] =
+                sizeof(uint32_t) * (size_t)ac_window_hits_words(jobs[j].n_kmers, jobs[j].sample.n_windows, ctx->max_errors);
+            mats.pos_bytes[j] = sizeof(uint32_t) * (size_t)ac_window_positions_words(jobs[j].n_kmers, jobs[j].sample.n_windows);
+            all += align256(mats.hits_bytes[j]);
+            all_pos += align256(mats.pos_bytes[j]);
+        }
+        AC_HIP(ctx, hipSetDevice(ctx->device));
+        if (ac_status st = grow(ctx, &ctx->d_hits, &ctx->d_hits_cap, all)) return st;
+        if (with_pos)
+            if (ac_status st = grow(ctx, &ctx->d_pos, &ctx->d_pos_cap, all_pos)) return st;
+        size_t at = 0, at_pos = 0;
+        for (uint32_t j = 0; j < n_jobs; ++j) {
+            const bool work = jobs[j].n_kmers && jobs[j].sample.n_windows;
+            mats.d_hits[j] = work ? (uint32_t*)((char*)ctx->d_hits + at) : nullptr;
+            at += align256(mats.hits_bytes[j]);
+            if (with_pos) {
+                mats.d_pos[j] = work ? (uint32_t*)((char*)ctx->d_pos + at_pos) : nullptr;
+                at_pos += align256(mats.pos_bytes[j]);
+            }
+        }
+    }
     bool stage_timeout = false;
-    const ac_status st = count_jobs_sync(ctx, k, jobs, n_jobs, true, &stage_timeout);
+    const ac_status st = count_jobs_sync(ctx, k, jobs, n_jobs, true, &stage_timeout, want_hits ? &mats : nullptr);
     // An early launch whose host inputs stopped arriving for 0.5 s (a stalled host: the kernel's waits
     // restart their clock on every bit of progress) skipped its work and said so: the call is run
     // again through the DMA path, which has no such wait, instead of failing.
     if (st != AC_OK && stage_timeout) {
         std::fprintf(stderr, "[approx_counter_amd] early launch timed out waiting for the host; retrying via DMA\n");
-        return count_jobs_sync(ctx, k, jobs, n_jobs, false, &stage_timeout);
+        // (with hits: the retry rewrites the matrices whole)
+        return count_jobs_sync(ctx, k, jobs, n_jobs, false, &stage_timeout, want_hits ? &mats : nullptr);
     }
     return st;
+}
+
+// ac_error_count_jobs_submit, and -- d_hits: one device matrix per job -- ac_window_hits_jobs_submit, and --
+// d_pos beside it -- ac_window_positions_jobs_submit.
+ac_status submit_jobs(ac_ctx* ctx, uint32_t k, const ac_job* jobs, uint32_t n_jobs, uint32_t* d_counts, void* hip_stream,
+                      uint32_t* const* d_hits, bool with_pos, uint32_t* const* d_pos);
+
+}  // namespace
+
+extern "C" {
+
+ac_status ac_error_count_jobs(ac_ctx* ctx, uint32_t k, const ac_job* jobs, uint32_t n_jobs) {
+    return count_jobs(ctx, k, jobs, n_jobs, nullptr, false, nullptr);
+}
+
+ac_status ac_window_hits_jobs(ac_ctx* ctx, uint32_t k, const ac_job* jobs, uint32_t n_jobs, uint32_t* const* hits_host) {
+    if (!ctx) return fail(nullptr, AC_ERR_INVALID, "ctx is NULL");
+    static uint32_t* const none[AC_MAX_JOBS] = {};
+    if (n_jobs && !hits_host) return fail(ctx, AC_ERR_INVALID, "window hits: hits_host is NULL");
+    return count_jobs(ctx, k, jobs, n_jobs, hits_host ? hits_host : none, false, nullptr);
+}
+
+ac_status ac_window_positions_jobs(ac_ctx* ctx, uint32_t k, const ac_job* jobs, uint32_t n_jobs,
+                                   uint32_t* const* hits_host, uint32_t* const* pos_host) {
+    if (!ctx) return fail(nullptr, AC_ERR_INVALID, "ctx is NULL");
+    static uint32_t* const none[AC_MAX_JOBS] = {};
+    if (n_jobs && !hits_host) return fail(ctx, AC_ERR_INVALID, "window hits: hits_host is NULL");
+    if (n_jobs && !pos_host) return fail(ctx, AC_ERR_INVALID, "window positions: pos_host is NULL");
+    return count_jobs(ctx, k, jobs, n_jobs, hits_host ? hits_host : none, true, pos_host ? pos_host : none);
+}
+
+ac_status ac_window_hits_jobs_submit(ac_ctx* ctx, uint32_t k, const ac_job* jobs, uint32_t n_jobs, uint32_t* d_counts,
+                                     uint32_t* const* d_hits, void* hip_stream) {
+    if (!ctx) return fail(nullptr, AC_ERR_INVALID, "ctx is NULL");
+    static uint32_t* const none[AC_MAX_JOBS] = {};
+    if (n_jobs && !d_hits) return fail(ctx, AC_ERR_INVALID, "window hits: d_hits is NULL");
+    return submit_jobs(ctx, k, jobs, n_jobs, d_counts, hip_stream, d_hits ? d_hits : none, false, nullptr);
+}
+
+ac_status ac_window_positions_jobs_submit(ac_ctx* ctx, uint32_t k, const ac_job* jobs, uint32_t n_jobs,
+                                          uint32_t* d_counts, uint32_t* const* d_hits, uint32_t* const* d_pos,
+                                          void* hip_stream) {
+    if (!ctx) return fail(nullptr, AC_ERR_INVALID, "ctx is NULL");
+    static uint32_t* const none[AC_MAX_JOBS] = {};
+    if (n_jobs && !d_hits) return fail(ctx, AC_ERR_INVALID, "window hits: d_hits is NULL");
+    if (n_jobs && !d_pos) return fail(ctx, AC_ERR_INVALID, "window positions: d_pos is NULL");
+    return submit_jobs(ctx, k, jobs, n_jobs, d_counts, hip_stream, d_hits ? d_hits : none, true, d_pos ? d_pos : none);
 }
 
 uint32_t ac_testing_stage_hooks(uint32_t flags) { return g_test_hooks.exchange(flags); }
@@ -921,7 +1080,21 @@ int ac_testing_last_count_kernel(ac_ctx* ctx) { return ctx ? ctx->last_kernel : 
 
 ac_status ac_error_count_jobs_submit(ac_ctx* ctx, uint32_t k, const ac_job* jobs, uint32_t n_jobs,
                                      uint32_t* d_counts, void* hip_stream) {
+    return submit_jobs(ctx, k, jobs, n_jobs, d_counts, hip_stream, nullptr, false, nullptr);
+}
+
+int ac_stage_mode(const ac_ctx* ctx) { return ctx ? ctx->last_mode : -1; }
+
+}  // extern "C"
+
+namespace {
+
+ac_status submit_jobs(ac_ctx* ctx, uint32_t k, const ac_job* jobs, uint32_t n_jobs, uint32_t* d_counts, void* hip_stream,
+                      uint32_t* const* d_hits, bool with_pos, uint32_t* const* d_pos) {
     if (ac_status st = check_jobs(ctx, k, jobs, n_jobs)) return st;
+    // (hits: the matrices' own refusal names the context first)
+    if (d_hits)
+        if (ac_status st = check_jobs_hits(ctx, k, jobs, n_jobs, d_hits, with_pos, d_pos)) return st;
     if (!ctx->peers.empty())
         return fail(ctx, AC_ERR_INVALID, "ac_error_count_jobs_submit needs a single-device context");
     uint64_t n_counts = 0;
@@ -960,7 +1133,7 @@ ac_status ac_error_count_jobs_submit(ac_ctx* ctx, uint32_t k, const ac_job* jobs
         // one part: the early launch, counts and errors into device memory (ac_check reads them)
         p.early = s.early;
         if (ac_status rc = stage_and_launch(ctx, k, jobs, p, st, d_counts, q, (parts > 1 && q == 0) ? 2u : 0u,
-                                            parts == 1))
+                                            parts == 1, d_hits, with_pos ? d_pos : nullptr))
             return rc;
         if (q > 0) AC_HIP(ctx, hipEventRecord(ctx->sub_ev[q], st));
         if (q == 0) ctx->last_mode = stage_mode_of(p);
@@ -974,6 +1147,4 @@ ac_status ac_error_count_jobs_submit(ac_ctx* ctx, uint32_t k, const ac_job* jobs
     return AC_OK;
 }
 
-int ac_stage_mode(const ac_ctx* ctx) { return ctx ? ctx->last_mode : -1; }
-
-}  // extern "C"
+}  // namespace

@@ -74,6 +74,11 @@ int stage_parts(uint64_t total_w) {
     return total_w >= STAGE_PARTS4_MIN_WINDOWS ? 4 : total_w >= STAGE_PARTS2_MIN_WINDOWS ? 2 : 1;
 }
 
+int stage_parts(uint64_t total_w, uint32_t hooks) {
+    const int parts = stage_parts(total_w);
+    return (hooks & AC_TESTING_TWO_PARTS) && parts < 2 ? 2 : parts;
+}
+
 std::vector<uint32_t> shard_cuts(const uint32_t* length, uint32_t n, size_t G) {
     uint64_t total = 0;
     for (uint32_t i = 0; i < n; ++i) total += length[i];
@@ -266,7 +271,18 @@ std::vector<Task> plan_stage(uint32_t k, const ac_job* jobs, JobPlan& p, bool ha
     {  // the launch's route decides whether it can count at the plan's edit budget
         bool live[AC_MAX_JOBS];
         for (uint32_t j = 0; j < p.n; ++j) live[j] = jobs[j].n_kmers && p.hi[j] > p.lo[j];
-        p.refusal = budget_refusal(p.max_errors, k, p.n, live, p.ulen);
+        p.refusal = nullptr;
+        // (hits first: its refusal names the hits call's own constraint)
+        if (p.want_hits)
+            p.refusal = p.want_pos ? positions_refusal(p.max_errors, k, p.n, live, p.ulen, p.multi_device, p.has_pos)
+                                   : hits_refusal(p.max_errors, k, p.n, live, p.ulen, p.multi_device);
+        if (!p.refusal) p.refusal = budget_refusal(p.max_errors, k, p.n, live, p.ulen);
+        for (uint32_t j = 0; j < p.n; ++j) {  // the launch's rows in the jobs' matrices
+            const uint64_t words = ((uint64_t)jobs[j].n_kmers + 31u) / 32u;
+            p.mat_windows[j] = jobs[j].sample.n_windows;
+            p.mat_row_off[j] = (uint64_t)p.lo[j] * words;
+            p.mat_plane[j] = (uint64_t)jobs[j].sample.n_windows * words;
+        }
     }
     layout_block(k, jobs, p, have_d_counts);
     if (p.early) early_regions(p, early_mode, hooks);

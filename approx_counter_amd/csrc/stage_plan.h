@@ -65,6 +65,18 @@ struct JobPlan {
     // plan, why this launch cannot (budget_refusal): the caller then fails the call instead of launching
     uint32_t max_errors = 2;
     const char* refusal = nullptr;
+    // Hits from the jobs stage (ac_window_hits_jobs / ac_window_positions_jobs; DESIGN.md §4e "Hits from the
+    // jobs stage"), set by the caller: this launch writes hit levels / end positions too, on a context of
+    // several devices or not, and which jobs came with a position matrix.  plan_stage then asks hits_refusal /
+    // positions_refusal of the launch (the answer in `refusal`, before the budget's) and says where the
+    // launch's rows lie in each job's matrices: job j's windows [lo[j], hi[j]) are rows lo[j].. of a matrix of
+    // mat_windows[j] = the job's n_windows rows -- mat_row_off[j] words from the matrix's start to the
+    // launch's first row in every plane, the planes mat_plane[j] words apart.  Row w of a job's matrix is the
+    // job's window w: the stage packs window i into slot i - lo[j] of the launch's image.
+    bool want_hits = false, want_pos = false, multi_device = false;
+    bool has_pos[AC_MAX_JOBS] = {};
+    uint32_t mat_windows[AC_MAX_JOBS] = {};
+    uint64_t mat_row_off[AC_MAX_JOBS] = {}, mat_plane[AC_MAX_JOBS] = {};
 };
 
 // Calls whose pack and DMA take hundreds of
@@ -78,6 +90,9 @@ struct JobPlan {
 // (profiles/r03_m14/parts_ab.log, round 3), not kept.
 constexpr uint64_t STAGE_PARTS2_MIN_WINDOWS = 1ull << 17, STAGE_PARTS4_MIN_WINDOWS = 1ull << 19;
 int stage_parts(uint64_t total_w);
+// ... and with the test hooks (approx_counter_amd_testing.h): AC_TESTING_TWO_PARTS cuts a call that would
+// take one part into two, whatever its size.
+int stage_parts(uint64_t total_w, uint32_t hooks);
 
 // Shard g of G of job windows [0, n): contiguous, balanced by bases (the rule
 // of ac_error_count's multi-device split and approx_counter_amd/shard.py).
@@ -122,7 +137,7 @@ using BlockRunner = void (*)(uint32_t n, const std::function<void(uint32_t)>& fn
 constexpr uint64_t SPAN_SCAN_SERIAL_MAX_WINDOWS = 1ull << 18;
 
 // Plans the launch of windows [p.lo[j], p.hi[j]) of jobs[0, p.n) (p.n, lo, hi, early, slot and scratch
-// set by the caller): cuts the packing tasks (the return value; of them the planner reads
+// set by the caller, with want_hits / want_pos / multi_device / has_pos): cuts the packing tasks (the return value; of them the planner reads
 // jobs[j].sample.length only), scans their spans, and fills in every other field of p but gen,
 // copiers and dp.  `have_d_counts`: the counts go to device memory (a submit), so no tagged
 // completion.  `pool_participants`: threads that will pack (caller included); `min_task_windows`: the

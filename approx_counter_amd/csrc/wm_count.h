@@ -165,12 +165,18 @@ struct LaunchArgs {
     // segment the device matrix the launch's hits kernel writes -- level e, window w, word c / 32 at
     // hits[(e * n_windows + w) * ceil(n_kmers / 32) + c / 32] -- read by that kernel family only.
     uint32_t* hits[AC_MAX_SEGS];
-    uint32_t want_hits;  // the launch runs a hits-writing kernel (plain bit-sliced launches only)
+    uint32_t want_hits;  // the launch runs a hits-writing kernel (bit-sliced launches only; staged: bshs_count.hip)
     // Match end positions (bsp_count.hip; DESIGN.md §4e "Match end positions"), appended again: per segment
     // the device matrix of eight bit planes -- bit c % 32 of pos[(b * n_windows + w) * ceil(n_kmers / 32) +
     // c / 32] is bit b of pos - 1, 0 where window w holds candidate c at no level -- written beside the hits.
     uint32_t* pos[AC_MAX_SEGS];
     uint32_t want_pos;  // the launch runs a hits-and-positions kernel (implies want_hits)
+    // Hits from the jobs stage (DESIGN.md §4e "Hits from the jobs stage"), appended again: per segment the window
+    // count of the MATRIX hits[i] / pos[i] point into -- the level planes (and position planes) lie mat_nw[i] *
+    // ceil(n_kmers / 32) words apart.  A whole-segment launch: the segment's n_windows.  A launch that counts
+    // windows [lo, hi) of a job (a part of a DMA-path call): the job's n_windows, and the host has folded the
+    // first row, lo * ceil(n_kmers / 32) words, into the pointers.
+    uint32_t mat_nw[AC_MAX_SEGS];
 };
 
 inline uint32_t pack_factor(uint32_t k) { return (32u / k) < AC_MAX_PACK ? (32u / k) : AC_MAX_PACK; }
@@ -249,6 +255,40 @@ constexpr int bsp_waves_per_simd(int k, int max_errors = 2) {
     return max_errors == 3 ? (k <= BSP3_K_MID ? 3 : k < BSP3_K_ONE ? 2 : 1)
                            : k <= 16 ? BSP_WAVES_PER_SIMD_16 : k <= BSP_K_MID ? 3 : 2;
 }
+// The staged hits-writing family (bshs_count.hip: the early launch and device packing of ac_window_hits_jobs)
+// and the staged hits-and-positions family (bsps_count.hip), re-derived per (K, rows) like the families above
+// (profiles/r15_bshs_codegen.txt): the staged frame's state costs registers the plain kernels do not hold.
+#ifndef BSHS_WAVES_PER_SIMD_16
+#define BSHS_WAVES_PER_SIMD_16 3  // three rows, k = 16: the staged counting kernel sits at exactly 128 VGPRs
+#endif
+#ifndef BSHS_K_MID
+#define BSHS_K_MID 23  // three rows: 3 waves for k = 18..BSHS_K_MID, then 2
+#endif
+#ifndef BSHS3_K_MID
+#define BSHS3_K_MID 19  // four rows: 3 waves up to here, then 2
+#endif
+constexpr int bshs_waves_per_simd(int k, int max_errors = 2) {
+    return max_errors == 3 ? (k <= BSHS3_K_MID ? 3 : 2) : k <= 16 ? BSHS_WAVES_PER_SIMD_16 : k <= BSHS_K_MID ? 3 : 2;
+}
+#ifndef BSPS_WAVES_PER_SIMD_16
+#define BSPS_WAVES_PER_SIMD_16 3
+#endif
+#ifndef BSPS_K_MID
+#define BSPS_K_MID 23  // three rows: 3 waves for k = 18..BSPS_K_MID but BSPS_K_TWO, then 2
+#endif
+#ifndef BSPS_K_TWO
+#define BSPS_K_TWO 22  // (k = 22 alone of 18..23 has scratch accesses inside the NFA block at 3 waves)
+#endif
+#ifndef BSPS3_K_MID
+#define BSPS3_K_MID 16  // four rows: 3 waves up to here (k = 18 spills inside the block at 3), then 2 ...
+#endif
+#ifndef BSPS3_K_ONE
+#define BSPS3_K_ONE 31  // ... and from here on 1, like the plain family
+#endif
+constexpr int bsps_waves_per_simd(int k, int max_errors = 2) {
+    return max_errors == 3 ? (k <= BSPS3_K_MID ? 3 : k < BSPS3_K_ONE ? 2 : 1)
+                           : k <= 16 ? BSPS_WAVES_PER_SIMD_16 : (k <= BSPS_K_MID && k != BSPS_K_TWO) ? 3 : 2;
+}
 hipError_t resident_waves_bs(uint32_t k, bool staged, int cu_count, uint32_t* waves, uint32_t max_errors = 2,
                              bool hits = false, bool pos = false);
 // bs3_count.hip: the E = 3 kernel for k (AC_BS_K_LIST), plain or staged; nullptr if there is none
@@ -262,6 +302,9 @@ hipError_t launch_hit_level_counts(const uint32_t* hits, uint32_t n_kmers, uint3
                                    uint32_t* level_counts, hipStream_t stream);
 // bsp_count.hip: the plain hits-and-positions kernel for k at edit budget max_errors; nullptr if there is none
 void (*bsp_kernel(uint32_t k, uint32_t max_errors))(LaunchArgs);
+// bshs_count.hip / bsps_count.hip: the staged hits-writing and hits-and-positions kernels, likewise
+void (*bshs_kernel(uint32_t k, uint32_t max_errors))(LaunchArgs);
+void (*bsps_kernel(uint32_t k, uint32_t max_errors))(LaunchArgs);
 // bsp_count.hip: profile[(d * n_kmers + c) * window_len + p - 1] = the windows that hold candidate c at
 // distance exactly d with their best occurrence ending at base p (1..window_len), from a hit matrix of
 // `levels` planes and its position matrix; profile is zeroed on the stream first

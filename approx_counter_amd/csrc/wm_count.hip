@@ -662,8 +662,8 @@ namespace {
 typedef void (*CountKernel)(LaunchArgs);
 CountKernel count_kernel(uint32_t P, uint32_t bs_k, bool staged, bool eq, uint32_t max_errors = 2u, bool hits = false,
                          bool pos = false) {
-    if (pos) return bs_k && !staged ? bsp_kernel(bs_k, max_errors) : nullptr;
-    if (hits) return bs_k && !staged ? bsh_kernel(bs_k, max_errors) : nullptr;
+    if (pos) return !bs_k ? nullptr : staged ? bsps_kernel(bs_k, max_errors) : bsp_kernel(bs_k, max_errors);
+    if (hits) return !bs_k ? nullptr : staged ? bshs_kernel(bs_k, max_errors) : bsh_kernel(bs_k, max_errors);
     if (bs_k && max_errors == 3u) return bs3_kernel(bs_k, staged);
     if (bs_k) {
 #define AC_BS_PICK(KK) \
@@ -733,8 +733,8 @@ hipError_t launch_wm2_count(const LaunchArgs& args, hipStream_t stream) {
     if (args.bs && !(args.eq && args.m)) return hipErrorInvalidValue;
     // (and only bit-sliced launches at another edit budget than 2)
     if (args.max_errors > 3u || (args.max_errors != 2u && !args.bs)) return hipErrorInvalidValue;
-    // (hits: plain bit-sliced launches only -- there is no other kernel that writes them)
-    if (args.want_hits && !(args.bs && !args.staged)) return hipErrorInvalidValue;
+    // (hits: bit-sliced launches only -- there is no other kernel that writes them)
+    if (args.want_hits && !args.bs) return hipErrorInvalidValue;
     if (args.want_pos && !args.want_hits) return hipErrorInvalidValue;
     const CountKernel kernel = count_kernel(args.P, args.bs ? args.m : 0u, args.staged != 0u, args.eq != 0u,
                                             args.max_errors, args.want_hits != 0u, args.want_pos != 0u);

@@ -489,7 +489,7 @@ uint32_t ac_max_errors(const ac_ctx* ctx);
  * ac_create_multi context, a NULL matrix for a segment that has work -- returns
  * AC_ERR_INVALID before anything is enqueued; ac_last_error names the
  * constraint.  Nothing falls back, and the context stays usable.  The jobs stage
- * (ac_error_count_jobs / _submit) does not produce hits.
+ * hands them out through calls of its own (ac_window_hits_jobs, below).
  */
 uint64_t ac_window_hits_words(uint32_t n_kmers, uint32_t n_windows, uint32_t max_errors);
 ac_status ac_window_hits_device(ac_ctx* ctx, uint32_t k, const ac_segment* segments, uint32_t n_segments,
@@ -543,6 +543,60 @@ ac_status ac_window_positions_samples(ac_ctx* ctx, uint32_t k, const ac_sample_j
 ac_status ac_hit_position_profile_device(ac_ctx* ctx, const uint32_t* hits, const uint32_t* pos, uint32_t n_kmers,
                                          uint32_t n_windows, uint32_t levels, uint32_t window_len, uint32_t* profile,
                                          void* hip_stream);
+
+/*
+ * Hit levels and end positions from the jobs stage (additive exports of ABI 8):
+ * ac_error_count_jobs / _submit -- Dna5 windows in, the whole errorCount stage --
+ * that also return the matrices above, from the same one launch: packing still
+ * overlaps counting, pinned samples (ac_host_alloc) are still packed by the
+ * kernel, and the launch still starts before the host has packed anything.
+ *   ac_window_hits_jobs        ac_error_count_jobs that also fills one host hit
+ *                              matrix per job (hits_host[j]); synchronous.  The
+ *                              launch writes context-owned device matrices, which
+ *                              the same stream then copies out: the call returns
+ *                              when every matrix is complete.
+ *   ac_window_positions_jobs   the same plus one host position matrix per job
+ *                              (pos_host[j]).
+ *   ac_window_hits_jobs_submit ac_error_count_jobs_submit that also stores into
+ *                              one device hit matrix per job (d_hits[j]) the
+ *                              caller gives; asynchronous on hip_stream, errors
+ *                              through ac_check.
+ *   ac_window_positions_jobs_submit
+ *                              the same plus one device position matrix per job
+ *                              (d_pos[j]).
+ * Layouts: exactly ac_window_hits_words / ac_window_positions_words u32 per job,
+ * as laid out above, at the context's budget E in 0..3.  Row w of job j's
+ * matrices is the job's window w in the caller's order (sample.offset[w] /
+ * length[w]): the stage packs window i into slot i.  The counts are stored as
+ * by ac_error_count_jobs / _submit and equal the set bits of the hit matrix.
+ * A job without k-mers or without windows has no work and may pass a NULL
+ * matrix; a NULL matrix for a job that has work is refused (AC_ERR_INVALID
+ * before anything is enqueued).
+ * Where they run: where the hit levels run -- k = 16 or 18..32, every job with
+ * work holding equal windows of 1..256 bases, AC_BITSLICE not 0, a single-device
+ * context -- on every route such a call takes: the early launch, device
+ * packing, the DMA path in one part or in several (each part writes its own
+ * rows of the matrices; every word is still written exactly once, with no
+ * clearing and no atomic).  Anything else -- ragged windows, a call mixing
+ * ragged and equal jobs, windows over 256 bases, k <= 15, k = 17,
+ * AC_BITSLICE=0, an ac_create_multi context -- returns AC_ERR_INVALID before
+ * anything is packed or enqueued, with the constraint in ac_last_error.  Nothing
+ * falls back, and the context stays usable.
+ * On a call that returns AC_OK every word of every matrix has been written.  On
+ * a call that returns an error (or whose ac_check does) -- a window reaching
+ * past its pinned block, a staging timeout the retry could not cure -- the
+ * matrices' contents are unspecified.  ac_stage_mode and ac_last_launch report
+ * as for the plain calls.
+ */
+ac_status ac_window_hits_jobs(ac_ctx* ctx, uint32_t k, const ac_job* jobs, uint32_t n_jobs,
+                              uint32_t* const* hits_host);
+ac_status ac_window_positions_jobs(ac_ctx* ctx, uint32_t k, const ac_job* jobs, uint32_t n_jobs,
+                                   uint32_t* const* hits_host, uint32_t* const* pos_host);
+ac_status ac_window_hits_jobs_submit(ac_ctx* ctx, uint32_t k, const ac_job* jobs, uint32_t n_jobs,
+                                     uint32_t* d_counts, uint32_t* const* d_hits, void* hip_stream);
+ac_status ac_window_positions_jobs_submit(ac_ctx* ctx, uint32_t k, const ac_job* jobs, uint32_t n_jobs,
+                                          uint32_t* d_counts, uint32_t* const* d_hits,
+                                          uint32_t* const* d_pos, void* hip_stream);
 
 #ifdef __cplusplus
 }

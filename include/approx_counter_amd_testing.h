@@ -33,6 +33,10 @@ extern "C" {
 /* Device packing (ABI 7) for every eligible job, whatever the call's size: the
  * default policy leaves small calls to the host pool. */
 #define AC_TESTING_DEVICE_PACK 8u
+/* A DMA-path jobs call (AC_STAGE_EARLY=0, or the retry of a timed-out early launch) with work is
+ * cut into two parts whatever its size; without the hook a call needs 2^17 windows for that
+ * (DESIGN.md §4c).  The parts of ac_window_hits_jobs write disjoint row ranges of one matrix. */
+#define AC_TESTING_TWO_PARTS 16u
 
 /* Sets the hooks (an OR of the flags above); returns the previous value. */
 uint32_t ac_testing_stage_hooks(uint32_t flags);

@@ -18,6 +18,8 @@ levels, DESIGN.md 4e "Hit levels") and prints the bytes of the matrices beside t
 times ac_hit_level_counts_device over the first segment's matrix and prints the rate its bytes were read at.
 --positions runs the hits-and-positions kernels instead (ac_window_positions_device, DESIGN.md 4e "Match end
 positions"); --profile then times ac_hit_position_profile_device over the first segment's two matrices.
+--staged --hits / --positions run the staged hits kernels (ac_window_hits_jobs_submit, DESIGN.md 4e "Hits from the
+jobs stage") on input sent ahead; --staged --time the staged counting kernel the same way, to set them against.
 """
 import argparse
 import os
@@ -68,8 +70,32 @@ def main():
         with ac.ApproxCounter(0, max_errors=a.max_errors) as c:
             prev = L.ac_testing_stage_hooks(2)  # AC_TESTING_ALL_AHEAD
             try:
-                for _ in range(a.warmup + a.launches):
-                    c.count_jobs(args.k, jobs)
+                if a.hits or a.time:
+                    # the submit forms: counts (and matrices) stay in device memory, so HIP events around the
+                    # calls time the copy ahead and the staged kernel alone -- with --hits / --positions the
+                    # staged hits kernels (ac_window_hits_jobs_submit / ac_window_positions_jobs_submit)
+                    jb = ac.Jobs(jobs)
+                    shapes = [(int(km.size), smp.n_windows) for km, smp in zip(jb.kmers, jb.samples)]
+                    mk = lambda n: torch.empty(max(n, 1), dtype=torch.int32, device="cuda")  # noqa: E731
+                    hits = [mk(ac.hits_words(nk, nw, a.max_errors)) for nk, nw in shapes] if a.hits else None
+                    pos = [mk(ac.positions_words(nk, nw)) for nk, nw in shapes] if a.positions else None
+                    out = mk(jb.n_counts)
+                    st = torch.cuda.current_stream()
+                    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    for i in range(a.warmup + a.launches):
+                        if i == a.warmup:
+                            t0.record()
+                        c.submit_jobs(args.k, jb, out, stream=st.cuda_stream, hits=hits, positions=pos)
+                    t1.record()
+                    torch.cuda.synchronize()
+                    c.check()
+                    mb = sum(t.numel() for t in (hits or []) + (pos or [])) * 4 / 1e6
+                    print(f"staged {'hits-and-positions' if a.positions else 'hits' if a.hits else 'counting'} kernel, "
+                          f"k = {args.k}, E = {a.max_errors}: mean launch {t0.elapsed_time(t1) / a.launches * 1e3:.1f} us "
+                          f"(copy ahead included), {mb:.1f} MB of matrices")
+                else:
+                    for _ in range(a.warmup + a.launches):
+                        c.count_jobs(args.k, jobs)
             finally:
                 L.ac_testing_stage_hooks(prev)
             print(f"{a.launches} staged launches of {a.config} on resident input (stage mode {c.stage_mode()}); "
