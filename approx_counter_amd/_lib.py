@@ -178,6 +178,17 @@ def load():
         L.ac_window_positions_jobs_submit.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ACJob), ctypes.c_uint32, p32, pp32,
                                                       pp32, vp]
         L.ac_window_positions_jobs_submit.restype = ctypes.c_int
+    if hasattr(L, "ac_hit_cooccurrence_words"):  # (an A/B build of an older library lacks the co-occurrence)
+        L.ac_hit_cooccurrence_words.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
+        L.ac_hit_cooccurrence_words.restype = ctypes.c_uint64
+        for fn in (L.ac_hit_cooccurrence_device, L.ac_hit_window_counts_device):
+            fn.argtypes = [vp, p32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, p32, vp]
+            fn.restype = ctypes.c_int
+        L.ac_hit_cooccurrence.argtypes = [vp, p32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, p32]
+        L.ac_hit_cooccurrence.restype = ctypes.c_int
+        L.ac_testing_hit_cooccurrence_stages.argtypes = [vp, p32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, p32,
+                                                         ctypes.c_uint32, vp]
+        L.ac_testing_hit_cooccurrence_stages.restype = ctypes.c_int
     L.ac_exact_path.argtypes = [vp]
     L.ac_exact_path.restype = ctypes.c_int
     pint = ctypes.POINTER(ctypes.c_int)

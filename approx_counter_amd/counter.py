@@ -141,6 +141,11 @@ def positions_words(n_kmers: int, n_windows: int) -> int:
     return 8 * int(n_windows) * ((int(n_kmers) + 31) // 32)
 
 
+def cooccurrence_words(n_kmers: int, levels: int = 1) -> int:
+    """ac_hit_cooccurrence_words: the u32 words of a co-occurrence result, levels x n_kmers x n_kmers."""
+    return int(levels) * int(n_kmers) * int(n_kmers)
+
+
 def unpack_positions(planes, hit_E, n_kmers: int) -> np.ndarray:
     """A position matrix's values: `planes` is (8, n_windows, words) uint32, plane b holding bit b of
     pos - 1; `hit_E` is bool (n_windows, n_kmers), the pairs within the budget (level E of the hit
@@ -212,6 +217,40 @@ class WindowHits:
     def level_counts(self) -> np.ndarray:
         """uint64 (E + 1, n_kmers): the windows within e edits of every k-mer; their sum over e is .counts."""
         return unpack_hits(self.levels, self.n_kmers).sum(axis=1, dtype=np.uint64)
+
+    def cooccurrence(self, e=None) -> np.ndarray:
+        """uint32 (n_kmers, n_kmers): entry (a, b) = the windows that hold k-mers a and b both within e edits
+        (default: the top level E); symmetric, its diagonal level_counts()[e].  Computed on the device
+        (ac_hit_cooccurrence_device) when the counter that made this object is attached, else with numpy."""
+        e = self.max_errors if e is None else int(e)
+        if not 0 <= e <= self.max_errors:
+            raise ValueError(f"level {e} is outside 0..{self.max_errors}")
+        nw = int(self.levels.shape[1])
+        if self._counter is None or not (self.n_kmers and nw):
+            h = self.hit(e).astype(np.float32)  # (exact: every sum is an integer below 2^24)
+            if nw >= 1 << 24:
+                h = h.astype(np.float64)
+            return (h.T @ h).astype(np.uint32)
+        import torch
+
+        dev = torch.device("cuda")
+        plane = torch.from_numpy(np.ascontiguousarray(self.levels[e]).view(np.int32)).to(dev)
+        out = self._counter.hit_cooccurrence(plane, self.n_kmers, nw, 1)
+        torch.cuda.synchronize(dev)
+        return out[0].cpu().numpy().view(np.uint32)
+
+    def window_counts(self) -> np.ndarray:
+        """uint32 (E + 1, n_windows): how many of the k-mers every window holds within e edits."""
+        lv, nw, _ = self.levels.shape
+        if self._counter is None or not (self.n_kmers and nw):
+            return unpack_hits(self.levels, self.n_kmers).sum(axis=2, dtype=np.uint32)
+        import torch
+
+        dev = torch.device("cuda")
+        h = torch.from_numpy(np.ascontiguousarray(self.levels).view(np.int32)).to(dev)
+        out = self._counter.hit_window_counts(h, self.n_kmers, nw, lv)
+        torch.cuda.synchronize(dev)
+        return out.cpu().numpy().view(np.uint32)
 
 
 class _PinnedBlock:
@@ -471,7 +510,7 @@ class ApproxCounter:
                                p[: positions_words(nk, nw)].reshape(8, nw, (nk + 31) // 32), L, self)
                     for c, m, p, (nk, nw, L) in zip(jobs.results(), mats, planes, shapes)]
         check(self._L.ac_window_hits_jobs(self._h, int(k), jobs.array, len(jobs.array), hp), self._h)
-        return [WindowHits(c, m[: hits_words(nk, nw, E)].reshape(E + 1, nw, (nk + 31) // 32), nk)
+        return [WindowHits(c, m[: hits_words(nk, nw, E)].reshape(E + 1, nw, (nk + 31) // 32), nk, counter=self)
                 for c, m, (nk, nw, _) in zip(jobs.results(), mats, shapes)]
 
     def _sample_jobs(self, fn, k, parts):
@@ -527,7 +566,8 @@ class ApproxCounter:
         a = (ACSampleJob * len(arr))(*arr)
         hp = (_lib.p32 * len(arr))(*[_ptr(m, ctypes.c_uint32) for m in mats])
         check(self._L.ac_window_hits_samples(self._h, int(k), a, len(arr), hp), self._h)
-        return [WindowHits(c[: km.size], m[: hits_words(km.size, nw, E)].reshape(E + 1, nw, (km.size + 31) // 32), km.size)
+        return [WindowHits(c[: km.size], m[: hits_words(km.size, nw, E)].reshape(E + 1, nw, (km.size + 31) // 32), km.size,
+                           counter=self)
                 for (km, c, nw), m in zip(keep, mats)]
 
     def _window_positions(self, k: int, parts) -> list:
@@ -574,6 +614,43 @@ class ApproxCounter:
         check(self._L.ac_hit_level_counts_device(self._h, p(hits), int(n_kmers), int(n_windows), int(levels), p(out),
                                                  ctypes.c_void_p(stream or 0)), self._h)
         return out[:, : int(n_kmers)]
+
+    def hit_cooccurrence(self, hits, n_kmers: int, n_windows: int, levels: int, stream=None):
+        """ac_hit_cooccurrence_device over a device hit matrix (a torch tensor of `levels` planes; a view at
+        plane e's offset with levels = 1 reduces that plane alone): returns an int32 device tensor
+        (levels, n_kmers, n_kmers), entry (e, a, b) = the windows of plane e that hold k-mers a and b both
+        (asynchronous)."""
+        import torch
+
+        n = int(n_kmers)
+        out = torch.empty((int(levels), n, n), dtype=torch.int32, device=hits.device)
+        p = lambda t: ctypes.cast(ctypes.c_void_p(t.data_ptr()), _lib.p32)  # noqa: E731
+        check(self._L.ac_hit_cooccurrence_device(self._h, p(hits), n, int(n_windows), int(levels), p(out),
+                                                 ctypes.c_void_p(stream or 0)), self._h)
+        return out
+
+    def hit_window_counts(self, hits, n_kmers: int, n_windows: int, levels: int, stream=None):
+        """ac_hit_window_counts_device over a device hit matrix: returns an int32 device tensor
+        (levels, n_windows), how many of the k-mers every window holds (asynchronous)."""
+        import torch
+
+        out = (torch.empty if int(n_kmers) else torch.zeros)((int(levels), int(n_windows)), dtype=torch.int32, device=hits.device)
+        p = lambda t: ctypes.cast(ctypes.c_void_p(t.data_ptr()), _lib.p32)  # noqa: E731
+        check(self._L.ac_hit_window_counts_device(self._h, p(hits), int(n_kmers), int(n_windows), int(levels), p(out),
+                                                  ctypes.c_void_p(stream or 0)), self._h)
+        return out
+
+    def cooccurrence_host(self, hits, n_kmers: int, n_windows: int, levels: int) -> np.ndarray:
+        """ac_hit_cooccurrence: a host hit matrix (uint32, `levels` planes) in, uint32 (levels, n_kmers,
+        n_kmers) out; synchronous (the command line's route)."""
+        m = np.ascontiguousarray(hits, dtype=np.uint32).reshape(-1)
+        n = int(n_kmers)
+        if m.size < hits_words(n, n_windows, int(levels) - 1):
+            raise ValueError("hit matrix smaller than (levels, n_windows, ceil(n_kmers / 32))")
+        out = np.full(max(cooccurrence_words(n, levels), 1), 0xFFFFFFFF, dtype=np.uint32)
+        check(self._L.ac_hit_cooccurrence(self._h, _ptr(m if m.size else np.zeros(1, np.uint32), ctypes.c_uint32), n,
+                                          int(n_windows), int(levels), _ptr(out, ctypes.c_uint32)), self._h)
+        return out[: cooccurrence_words(n, levels)].reshape(int(levels), n, n)
 
     def exact_path(self) -> int:
         """ac_exact_path: 1 partitioned, 0 hash table, -1 no exact count yet."""

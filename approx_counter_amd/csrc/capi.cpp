@@ -288,6 +288,8 @@ void ac_destroy(ac_ctx* ctx) {
     if (ctx->d_stage) (void)hipFree(ctx->d_stage);
     if (ctx->d_hits) (void)hipFree(ctx->d_hits);
     if (ctx->d_pos) (void)hipFree(ctx->d_pos);
+    if (ctx->d_cooc) (void)hipFree(ctx->d_cooc);
+    if (ctx->d_cooc_io) (void)hipFree(ctx->d_cooc_io);
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
     for (auto& sc : ctx->sc) {
         if (sc.queue) (void)hipFree(sc.queue);

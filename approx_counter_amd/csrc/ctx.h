@@ -34,6 +34,12 @@ struct ac_ctx {
     // ac_window_positions_samples / ac_window_positions_jobs: the jobs' device position matrices, likewise
     void* d_pos = nullptr;
     size_t d_pos_cap = 0;
+    // ac_hit_cooccurrence*: the transposed planes the product reads (grow-only; stream-ordered like the
+    // count scratch), and the host-buffer call's device matrix and result, back to back
+    void* d_cooc = nullptr;
+    size_t d_cooc_cap = 0;
+    void* d_cooc_io = nullptr;
+    size_t d_cooc_io_cap = 0;
     // ac_error_count staging: the inputs packed back to back in pinned host
     // memory, one H2D copy into d_stage, counts copied back into the same
     // pinned block (grow-only)

@@ -17,6 +17,9 @@
 //   --positions     beside every <out>_<run>.<end> file a <out>_<run>.<end>.positions file: per k-mer, in the
 //                   same order, for every base 1..L of the sampled windows how many of the windows within E
 //                   edits have their best occurrence ending there (ac_window_positions_samples)
+//   --cooccurrence  beside every <out>_<run>.<end> file a <out>_<run>.<end>.cooc file: per k-mer, in the same
+//                   order, for every k-mer of the file how many sampled windows hold the two together within
+//                   E edits (two of the reference's bitfields at once; ac_hit_cooccurrence)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -94,6 +97,11 @@ const Opt OPTS[] = {
      "k-mer and, for every base 1 to L of the sampled windows, the number of windows holding it within max-errors "
      "edits whose leftmost best occurrence ends at that base (they sum to the last column of its .levels line). "
      "Same needs as --levels, with which it can be combined."},
+    {"", "cooccurrence", Kind::Flag,
+     "[MI355X build] also write <out>_<run>.<end>.cooc: one line per k-mer of the main file, in its order, the "
+     "k-mer and, for every k-mer of the main file in the same order, the number of sampled windows holding both "
+     "within max-errors edits (entry i of line i is the last column of its .levels line). Same needs as --levels, "
+     "with which and with --positions it can be combined."},
     {"", "host-exact", Kind::Flag,
      "[MI355X build] the reference's host stages: whole reads in memory, exact k-mer count on the CPU"},
     {"", "dump-sample", Kind::String,
@@ -295,6 +303,28 @@ bool export_positions(const pair_vector& ranked, const std::vector<uint64_t>& km
     return std::fclose(f) == 0;
 }
 
+// --cooccurrence: one line per k-mer of `ranked`, the k-mer and one count per k-mer of `ranked` in the same
+// order -- `cooc` is the n x n result of ac_hit_cooccurrence over the job's top level plane, candidate c =
+// kmers[c], permuted here into the main file's order.
+bool export_cooccurrence(const pair_vector& ranked, const std::vector<uint64_t>& kmers, const std::vector<uint32_t>& cooc,
+                         uint32_t k, const std::string& path) {
+    const size_t n = kmers.size();
+    std::map<uint64_t, uint32_t> index;  // (the exact count's k-mers are distinct)
+    for (uint32_t c = 0; c < n; ++c) index.emplace(kmers[c], c);
+    std::vector<uint32_t> order;
+    for (const auto& kv : ranked) order.push_back(index.at(kv.first));
+    std::FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) return false;
+    std::string line;
+    for (size_t i = 0; i < order.size(); ++i) {
+        line = int2dna(ranked[i].first, k);
+        for (const uint32_t c : order) line += '\t' + std::to_string(cooc[(size_t)order[i] * n + c]);
+        line += '\n';
+        std::fwrite(line.data(), 1, line.size(), f);
+    }
+    return std::fclose(f) == 0;
+}
+
 void open_devices(Devices& dev, uint64_t n_gpus, uint64_t max_errors) {
     if (dev.ctx) return;
     if (n_gpus < 1) n_gpus = 1;
@@ -384,6 +414,7 @@ int main(int argc, char const** argv) {
     const bool host_exact = args.val.count("host-exact") > 0;
     const bool levels = args.val.count("levels") > 0;
     const bool positions = args.val.count("positions") > 0;
+    const bool cooccurrence = args.val.count("cooccurrence") > 0;
     std::string dump_sample;
     get_option(args, "dump-sample", dump_sample);
     const std::string input_file = args.input;
@@ -424,8 +455,9 @@ int main(int argc, char const** argv) {
     // (ac_window_hits_samples); what only the sample can tell -- read ends of unequal length -- the
     // library refuses when the count is asked for.
     // --positions: the same kernels' sibling family, the same constraints and messages.
-    for (const char* flag : {"--levels", "--positions"}) {
-        if (!(flag[2] == 'l' ? levels : positions)) continue;
+    // --cooccurrence: a reduction of the same hit matrix, so the same again.
+    for (const char* flag : {"--levels", "--positions", "--cooccurrence"}) {
+        if (!(flag[2] == 'l' ? levels : flag[2] == 'p' ? positions : cooccurrence)) continue;
         const char* why = !(k == 16 || (k >= 18 && k <= 32)) ? " needs a kmer size (-k) of 16 or 18 to 32"
                           : sl > 255                         ? " needs a sampling length (-sl) of at most 255"
                           : n_gpus > 1                       ? " needs one GPU (-g 1)"
@@ -518,12 +550,14 @@ int main(int argc, char const** argv) {
             // --positions: the positions call, which yields the counts and the levels as well
             std::vector<std::vector<uint32_t>> pos(pending.size());
             std::vector<uint32_t*> pos_p(pending.size());
+            // --cooccurrence: the hits call as well, then the top level plane's co-occurrence
+            std::vector<std::vector<uint32_t>> cooc(pending.size());
             try {
                 devices();
                 const bool on_device = !host_exact && dev.shards == 1;  // the samples uploaded for the exact count
                 for (size_t e = 0; e < pending.size(); ++e)
                     jobs[e].sample = on_device ? pending[e].dsample : view(pending[e].img);
-                if (levels || positions)
+                if (levels || positions || cooccurrence)
                     for (size_t e = 0; e < pending.size(); ++e) {
                         hits[e].assign((size_t)ac_window_hits_words(jobs[e].n_kmers, jobs[e].sample.n_windows,
                                                                     (uint32_t)max_errors) + 1, 0u);
@@ -536,10 +570,20 @@ int main(int argc, char const** argv) {
                 const ac_status st =
                     positions   ? ac_window_positions_samples(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size(),
                                                               hits_p.data(), pos_p.data())
-                    : levels    ? ac_window_hits_samples(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size(), hits_p.data())
+                    : levels || cooccurrence
+                        ? ac_window_hits_samples(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size(), hits_p.data())
                     : on_device ? ac_error_count_samples(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size())
                                 : ac_error_count_images(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size());
                 if (st != AC_OK) throw std::runtime_error(ac_last_error(dev.ctx));
+                if (cooccurrence)
+                    for (size_t e = 0; e < pending.size(); ++e) {
+                        const uint32_t n = jobs[e].n_kmers, nw = jobs[e].sample.n_windows;
+                        cooc[e].assign((size_t)ac_hit_cooccurrence_words(n, 1) + 1, 0u);
+                        // (plane E of the E + 1: one plane is ac_window_hits_words at budget 0)
+                        const uint32_t* top = hits[e].data() + (size_t)max_errors * (size_t)ac_window_hits_words(n, nw, 0u);
+                        if (ac_hit_cooccurrence(dev.ctx, top, n, nw, 1u, cooc[e].data()) != AC_OK)
+                            throw std::runtime_error(ac_last_error(dev.ctx));
+                    }
             } catch (const std::exception& e) {
                 std::cerr << error_pref << "approximate count failed: " << e.what() << std::endl;
                 return false;
@@ -567,6 +611,11 @@ int main(int argc, char const** argv) {
                                       (uint32_t)k, path + ".positions")) {
                     std::cerr << error_pref + "Failed to export the match end positions" << std::endl;
                     std::cerr << "Path: " << path + ".positions" << std::endl;
+                    return false;
+                }
+                if (cooccurrence && !export_cooccurrence(sorted_error_count, km[e], cooc[e], (uint32_t)k, path + ".cooc")) {
+                    std::cerr << error_pref + "Failed to export the co-occurrence" << std::endl;
+                    std::cerr << "Path: " << path + ".cooc" << std::endl;
                     return false;
                 }
                 if (mr_v > 0) print("Done", tab_level);

@@ -310,6 +310,17 @@ void (*bsps_kernel(uint32_t k, uint32_t max_errors))(LaunchArgs);
 // `levels` planes and its position matrix; profile is zeroed on the stream first
 hipError_t launch_hit_position_profile(const uint32_t* hits, const uint32_t* pos, uint32_t n_kmers, uint32_t n_windows,
                                        uint32_t levels, uint32_t window_len, uint32_t* profile, hipStream_t stream);
+// hit_cooc.hip: cooc[(e * n_kmers + a) * n_kmers + b] = the windows of level plane e of a hit matrix that hold
+// candidates a and b both.  stages bit 0: the planes' transposition into `scratch`
+// (hit_cooc_scratch_words u32); bit 1: the product from scratch into cooc, every word of which is then
+// defined (zeroed on the stream first where the launch rule splits the window axis).  3 = the whole call.
+uint64_t hit_cooc_scratch_words(uint32_t n_kmers, uint32_t n_windows, uint32_t levels);
+hipError_t launch_hit_cooccurrence(const uint32_t* hits, uint32_t n_kmers, uint32_t n_windows, uint32_t levels,
+                                   uint32_t* scratch, uint32_t* cooc, uint32_t stages, hipStream_t stream);
+// hit_cooc.hip: window_counts[e * n_windows + w] = the candidates < n_kmers that row w of plane e holds; every
+// word stored once
+hipError_t launch_hit_window_counts(const uint32_t* hits, uint32_t n_kmers, uint32_t n_windows, uint32_t levels,
+                                    uint32_t* window_counts, hipStream_t stream);
 
 // Waves of the count kernel for pattern pack P that fit on the device at once.
 hipError_t resident_waves(uint32_t P, bool staged, int cu_count, uint32_t* waves);

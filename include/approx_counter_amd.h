@@ -598,6 +598,58 @@ ac_status ac_window_positions_jobs_submit(ac_ctx* ctx, uint32_t k, const ac_job*
                                           uint32_t* d_counts, uint32_t* const* d_hits,
                                           uint32_t* const* d_pos, void* hip_stream);
 
+/*
+ * Co-occurrence: which k-mers share windows (additive exports of ABI 8).  The
+ * reference's per-read bitfields tcount[errors][read] (approx_counter.cpp:553-565)
+ * are collapsed by vectorSum into one count per k-mer (580-596); the hit levels
+ * above hand them out, and their reductions so far (ac_hit_level_counts_device,
+ * ac_hit_position_profile_device) are per k-mer as well.  These calls reduce a
+ * hit matrix over pairs of k-mers, and over the k-mers of a window.
+ * Input: `hits`, a matrix in exactly the layout of ac_window_hits_words --
+ * `levels` (1..4) planes of n_windows rows of words = ceil(n_kmers / 32) u32,
+ * bit c % 32 of word c / 32 = candidate c.  Bits of candidates >= n_kmers in a
+ * row's last word may hold anything and are ignored.  To reduce one plane e of
+ * a larger matrix pass hits + e * n_windows * words with levels = 1.
+ *   ac_hit_cooccurrence_words    u32 words of a result: levels * n_kmers * n_kmers
+ *                                (64-bit)
+ *   ac_hit_cooccurrence_device   cooc[(e * n_kmers + a) * n_kmers + b] = the
+ *                                windows whose row of plane e has bit a and bit
+ *                                b both set: symmetric, its diagonal the
+ *                                level_counts[e * n_kmers + a] of
+ *                                ac_hit_level_counts_device; u32 values (<=
+ *                                n_windows), every index computed in 64 bits.
+ *                                hits and cooc are device memory; asynchronous
+ *                                on hip_stream.
+ *   ac_hit_cooccurrence          the same over host buffers (the command line's
+ *                                route): the matrix is uploaded into context
+ *                                scratch, reduced on the context's stream and
+ *                                copied back; synchronous.
+ *   ac_hit_window_counts_device  window_counts[e * n_windows + w] = the
+ *                                candidates c < n_kmers whose bit is set in row
+ *                                w of plane e -- the other marginal: how many of
+ *                                the k-mers a window holds.  Device memory,
+ *                                asynchronous on hip_stream.
+ * Every word of a result is defined on return (of the stream work): the caller
+ * clears nothing.  n_windows = 0 writes zeros; n_kmers = 0 is no work.
+ * A NULL ctx, levels outside 1..4, a NULL output with n_kmers > 0 and
+ * a NULL hits with n_kmers and n_windows both > 0 return AC_ERR_INVALID before
+ * anything is enqueued, with the constraint in ac_last_error.
+ * Where they run: on any context, whichever count kernel wrote the matrix and
+ * whatever AC_BITSLICE, k and the edit budget are; an ac_create_multi context
+ * uses its first device.  The product reads the planes transposed, from
+ * context-owned scratch that is grown on demand (AC_ERR_NOMEM if it cannot be;
+ * the context stays usable), freed by ac_destroy and stream-ordered like the
+ * count scratch: no two launches of one context on different streams at the
+ * same time.
+ */
+uint64_t ac_hit_cooccurrence_words(uint32_t n_kmers, uint32_t levels);
+ac_status ac_hit_cooccurrence_device(ac_ctx* ctx, const uint32_t* hits, uint32_t n_kmers, uint32_t n_windows,
+                                     uint32_t levels, uint32_t* cooc, void* hip_stream);
+ac_status ac_hit_cooccurrence(ac_ctx* ctx, const uint32_t* hits_host, uint32_t n_kmers, uint32_t n_windows,
+                              uint32_t levels, uint32_t* cooc_host);
+ac_status ac_hit_window_counts_device(ac_ctx* ctx, const uint32_t* hits, uint32_t n_kmers, uint32_t n_windows,
+                                      uint32_t levels, uint32_t* window_counts, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,6 +47,12 @@ uint32_t ac_testing_stage_hooks(uint32_t flags);
  * shard 0's. */
 int ac_testing_last_count_kernel(ac_ctx* ctx);
 
+/* ac_hit_cooccurrence_device in steps, for measurement (tools/kernel_run.py --cooc): stages 1 = only the
+ * planes' transposition into the context's scratch, 2 = only the product from the scratch an earlier call
+ * with the same shape filled, 3 = both (the product call itself). */
+ac_status ac_testing_hit_cooccurrence_stages(ac_ctx* ctx, const uint32_t* hits, uint32_t n_kmers, uint32_t n_windows,
+                                             uint32_t levels, uint32_t* cooc, uint32_t stages, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,10 @@ levels, DESIGN.md 4e "Hit levels") and prints the bytes of the matrices beside t
 times ac_hit_level_counts_device over the first segment's matrix and prints the rate its bytes were read at.
 --positions runs the hits-and-positions kernels instead (ac_window_positions_device, DESIGN.md 4e "Match end
 positions"); --profile then times ac_hit_position_profile_device over the first segment's two matrices.
+--cooc (with --hits or --positions) then times the co-occurrence of the first segment's top level plane on the
+resident matrix (ac_hit_cooccurrence_device, DESIGN.md 4e "Co-occurrence"): the transposition and the product on
+their own (ac_testing_hit_cooccurrence_stages) and the whole call, beside the level counter on the same plane and
+the op model n (n + 1) / 2 x ceil(W / 32) x 2 lane-ops against bench.py's VALU peak.
 --staged --hits / --positions run the staged hits kernels (ac_window_hits_jobs_submit, DESIGN.md 4e "Hits from the
 jobs stage") on input sent ahead; --staged --time the staged counting kernel the same way, to set them against.
 """
@@ -52,6 +56,9 @@ def main():
                     help="the hits-and-positions kernels (ac_window_positions_device); implies --hits")
     ap.add_argument("--profile", action="store_true",
                     help="with --positions: also time ac_hit_position_profile_device over the first segment's matrices")
+    ap.add_argument("--cooc", action="store_true",
+                    help="with --hits / --positions: also time ac_hit_cooccurrence_device over the first segment's top "
+                         "level plane: transposition, product and the whole call")
     a = ap.parse_args()
     a.hits = a.hits or a.positions
     import torch
@@ -143,6 +150,40 @@ def main():
             print(f"level counts of {4 * words[0]} bytes ({s0.n_kmers} k-mers x {s0.n_windows} windows x "
                   f"{a.max_errors + 1} levels): {ms:.4f} ms per call (memset + kernel), "
                   f"{4 * words[0] / ms / 1e6:.1f} GB/s read")
+        if a.hits and a.cooc:
+            import ctypes
+
+            from approx_counter_amd import _lib
+
+            s0 = segs[0]
+            n, nw, E = s0.n_kmers, s0.n_windows, a.max_errors
+            top = hits[0][E * nw * ((n + 31) // 32):]  # (the single-plane idiom: plane E with levels = 1)
+            out = torch.empty(max(n * n, 1), dtype=torch.int32, device="cuda")
+            p = lambda t: ctypes.cast(ctypes.c_void_p(t.data_ptr()), _lib.p32)  # noqa: E731
+            ms = {}
+            for name, stages in (("transposition", 1), ("product", 2), ("both", 3)):
+                for i in range(a.warmup + a.launches):
+                    if i == a.warmup:
+                        t0.record()
+                    _lib.check(c._L.ac_testing_hit_cooccurrence_stages(c.handle, p(top), n, nw, 1, p(out), stages, None), c.handle)
+                t1.record()
+                torch.cuda.synchronize()
+                ms[name] = t0.elapsed_time(t1) / a.launches
+            for i in range(a.warmup + a.launches):
+                if i == a.warmup:
+                    t0.record()
+                lc = c.hit_level_counts(top, n, nw, 1)
+            t1.record()
+            torch.cuda.synchronize()
+            ms["level counts"] = t0.elapsed_time(t1) / a.launches
+            co = out[: n * n].view(n, n)
+            assert (co.diagonal() == lc[0]).all(), "the diagonal is not the level counts"
+            assert (co == co.t()).all(), "the co-occurrence is not symmetric"
+            ops = n * (n + 1) // 2 * ((nw + 31) // 32) * 2
+            print(f"co-occurrence of plane {E} ({n} k-mers x {nw} windows, {4 * nw * ((n + 31) // 32)} bytes in, {4 * n * n} out): "
+                  + ", ".join(f"{k} {v:.4f} ms" for k, v in ms.items())
+                  + f" per call; op model {ops:.3e} lane-ops = {ops / bench.VALU_PEAK_OPS * 1e3:.4f} ms at the VALU peak, "
+                  f"{ops / bench.VALU_PEAK_OPS * 1e3 / ms['product'] * 100:.1f} % of the product's time")
         if a.positions and a.profile:
             s0 = segs[0]
             for i in range(a.warmup + a.launches):
