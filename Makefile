@@ -30,12 +30,12 @@ OBJDIR := build/obj
 endif
 
 # the C-ABI layer: host code over the HIP runtime (hipcc as a C++ compiler: no kernel in these) ...
-CAPI := capi count_launch capi_exact capi_comm capi_cooc
+CAPI := capi count_launch capi_exact capi_comm capi_cooc capi_cross
 # ... and plain host C++ (g++): the worker pool + AVX packer, the jobs stage's plan
 HOSTONLY := host_pack stage_plan
 HDRS := $(INC)/approx_counter_amd.h $(INC)/approx_counter_amd_testing.h $(CSRC)/wm_count.h $(CSRC)/exact_count.h \
 	$(CSRC)/host_pack.h $(CSRC)/nrec.h $(CSRC)/ctx.h $(CSRC)/stage_plan.h $(CSRC)/bs_nfa.h $(CSRC)/bs_nfa_r.h \
-	$(CSRC)/hit_levels.h $(CSRC)/bs_pos.h $(CSRC)/hit_cooc.h
+	$(CSRC)/hit_levels.h $(CSRC)/bs_pos.h $(CSRC)/hit_cooc.h $(CSRC)/hit_cross.h
 INCS := -I$(INC) -I$(CSRC)
 # host-only code that includes the HIP headers (no kernel, no <<<>>>)
 HIP_HOST := -D__HIP_PLATFORM_AMD__ -I$(ROCM_PATH)/include
@@ -105,7 +105,7 @@ $(HOSTONLY:%=$(OBJDIR)/%.o): $(OBJDIR)/%.o: $(CSRC)/%.cpp $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(CXX) $(HOST_CXXFLAGS) $(HIP_HOST) $(INCS) -c $< -o $@
 
-$(LIB): $(OBJDIR)/wm_count.o $(OBJDIR)/bs3_count.o $(OBJDIR)/bsh_count.o $(OBJDIR)/bsp_count.o $(OBJDIR)/bshs_count.o $(OBJDIR)/bsps_count.o $(OBJDIR)/hit_cooc.o $(OBJDIR)/exact_count.o $(OBJDIR)/jobs_stage.o $(CAPI:%=$(OBJDIR)/%.o) $(HOSTONLY:%=$(OBJDIR)/%.o)
+$(LIB): $(OBJDIR)/wm_count.o $(OBJDIR)/bs3_count.o $(OBJDIR)/bsh_count.o $(OBJDIR)/bsp_count.o $(OBJDIR)/bshs_count.o $(OBJDIR)/bsps_count.o $(OBJDIR)/hit_cooc.o $(OBJDIR)/hit_cross.o $(OBJDIR)/exact_count.o $(OBJDIR)/jobs_stage.o $(CAPI:%=$(OBJDIR)/%.o) $(HOSTONLY:%=$(OBJDIR)/%.o)
 	@mkdir -p $(dir $@)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -pthread
 
@@ -130,6 +130,7 @@ asm: $(WM_SRC) $(HDRS)
 	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) --cuda-device-only -S $(CSRC)/bshs_count.hip -o build/asm/bshs_count.s
 	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) --cuda-device-only -S $(CSRC)/bsps_count.hip -o build/asm/bsps_count.s
 	$(HIPCC) $(HIPFLAGS) $(INCS) --cuda-device-only -S $(CSRC)/hit_cooc.hip -o build/asm/hit_cooc.s
+	$(HIPCC) $(HIPFLAGS) $(INCS) --cuda-device-only -S $(CSRC)/hit_cross.hip -o build/asm/hit_cross.s
 
 clean:
 	rm -rf build $(LIBDIR) $(BINDIR) oracle/_build

@@ -189,6 +189,16 @@ def load():
         L.ac_testing_hit_cooccurrence_stages.argtypes = [vp, p32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, p32,
                                                          ctypes.c_uint32, vp]
         L.ac_testing_hit_cooccurrence_stages.restype = ctypes.c_int
+    if hasattr(L, "ac_hit_cross_cooccurrence_words"):  # (likewise the cross co-occurrence)
+        u32 = ctypes.c_uint32
+        L.ac_hit_cross_cooccurrence_words.argtypes = [u32, u32, u32]
+        L.ac_hit_cross_cooccurrence_words.restype = ctypes.c_uint64
+        L.ac_hit_cross_cooccurrence_device.argtypes = [vp, p32, u32, p32, u32, u32, u32, p32, vp]
+        L.ac_hit_cross_cooccurrence_device.restype = ctypes.c_int
+        L.ac_hit_cross_cooccurrence.argtypes = [vp, p32, u32, p32, u32, u32, u32, p32]
+        L.ac_hit_cross_cooccurrence.restype = ctypes.c_int
+        L.ac_testing_hit_cross_stages.argtypes = [vp, p32, u32, p32, u32, u32, u32, p32, u32, vp]
+        L.ac_testing_hit_cross_stages.restype = ctypes.c_int
     L.ac_exact_path.argtypes = [vp]
     L.ac_exact_path.restype = ctypes.c_int
     pint = ctypes.POINTER(ctypes.c_int)

@@ -146,6 +146,11 @@ def cooccurrence_words(n_kmers: int, levels: int = 1) -> int:
     return int(levels) * int(n_kmers) * int(n_kmers)
 
 
+def cross_cooccurrence_words(n_a: int, n_b: int, levels: int = 1) -> int:
+    """ac_hit_cross_cooccurrence_words: the u32 words of a cross co-occurrence result, levels x n_a x n_b."""
+    return int(levels) * int(n_a) * int(n_b)
+
+
 def unpack_positions(planes, hit_E, n_kmers: int) -> np.ndarray:
     """A position matrix's values: `planes` is (8, n_windows, words) uint32, plane b holding bit b of
     pos - 1; `hit_E` is bool (n_windows, n_kmers), the pairs within the budget (level E of the hit
@@ -236,6 +241,35 @@ class WindowHits:
         dev = torch.device("cuda")
         plane = torch.from_numpy(np.ascontiguousarray(self.levels[e]).view(np.int32)).to(dev)
         out = self._counter.hit_cooccurrence(plane, self.n_kmers, nw, 1)
+        torch.cuda.synchronize(dev)
+        return out[0].cpu().numpy().view(np.uint32)
+
+    def cross_cooccurrence(self, other, e=None, e_other=None) -> np.ndarray:
+        """uint32 (self.n_kmers, other.n_kmers): entry (a, b) = the windows that hold this object's k-mer a
+        within e edits and `other`'s k-mer b within e_other edits (defaults: each object's top level).  The
+        two objects must be over the same windows, row w of both the same read (two parts over paired
+        windows, or the same object twice: wh.cross_cooccurrence(wh, 0, wh.max_errors) pairs two levels).
+        Computed on the device (ac_hit_cross_cooccurrence_device) when either object has its counter attached,
+        else with numpy."""
+        e = self.max_errors if e is None else int(e)
+        e_other = other.max_errors if e_other is None else int(e_other)
+        if not 0 <= e <= self.max_errors:
+            raise ValueError(f"level {e} is outside 0..{self.max_errors}")
+        if not 0 <= e_other <= other.max_errors:
+            raise ValueError(f"level {e_other} of the other matrix is outside 0..{other.max_errors}")
+        nw = int(self.levels.shape[1])
+        if int(other.levels.shape[1]) != nw:
+            raise ValueError(f"the two matrices hold {nw} and {int(other.levels.shape[1])} windows: not the same reads")
+        counter = self._counter if self._counter is not None else other._counter
+        if counter is None or not (self.n_kmers and other.n_kmers and nw):
+            dt = np.float64 if nw >= 1 << 24 else np.float32  # (float32 is exact: every sum is an integer below 2^24)
+            return (self.hit(e).astype(dt).T @ other.hit(e_other).astype(dt)).astype(np.uint32)
+        import torch
+
+        dev = torch.device("cuda")
+        a = torch.from_numpy(np.ascontiguousarray(self.levels[e]).view(np.int32)).to(dev)
+        b = torch.from_numpy(np.ascontiguousarray(other.levels[e_other]).view(np.int32)).to(dev)
+        out = counter.hit_cross_cooccurrence(a, self.n_kmers, b, other.n_kmers, nw, 1)
         torch.cuda.synchronize(dev)
         return out[0].cpu().numpy().view(np.uint32)
 
@@ -629,6 +663,20 @@ class ApproxCounter:
                                                  ctypes.c_void_p(stream or 0)), self._h)
         return out
 
+    def hit_cross_cooccurrence(self, hits_a, n_a: int, hits_b, n_b: int, n_windows: int, levels: int, stream=None):
+        """ac_hit_cross_cooccurrence_device over two device hit matrices of the same n_windows (torch tensors of
+        `levels` planes each; views at two planes' offsets with levels = 1 pair those planes): returns an int32
+        device tensor (levels, n_a, n_b), entry (e, a, b) = the windows of plane e that hold k-mer a of the
+        first matrix and k-mer b of the second (asynchronous)."""
+        import torch
+
+        na, nb = int(n_a), int(n_b)
+        out = torch.empty((int(levels), na, nb), dtype=torch.int32, device=hits_a.device)
+        p = lambda t: ctypes.cast(ctypes.c_void_p(t.data_ptr()), _lib.p32)  # noqa: E731
+        check(self._L.ac_hit_cross_cooccurrence_device(self._h, p(hits_a), na, p(hits_b), nb, int(n_windows), int(levels),
+                                                       p(out), ctypes.c_void_p(stream or 0)), self._h)
+        return out
+
     def hit_window_counts(self, hits, n_kmers: int, n_windows: int, levels: int, stream=None):
         """ac_hit_window_counts_device over a device hit matrix: returns an int32 device tensor
         (levels, n_windows), how many of the k-mers every window holds (asynchronous)."""
@@ -651,6 +699,22 @@ class ApproxCounter:
         check(self._L.ac_hit_cooccurrence(self._h, _ptr(m if m.size else np.zeros(1, np.uint32), ctypes.c_uint32), n,
                                           int(n_windows), int(levels), _ptr(out, ctypes.c_uint32)), self._h)
         return out[: cooccurrence_words(n, levels)].reshape(int(levels), n, n)
+
+    def cross_cooccurrence_host(self, hits_a, n_a: int, hits_b, n_b: int, n_windows: int, levels: int) -> np.ndarray:
+        """ac_hit_cross_cooccurrence: two host hit matrices (uint32, `levels` planes each, the same n_windows)
+        in, uint32 (levels, n_a, n_b) out; synchronous (the command line's route)."""
+        a = np.ascontiguousarray(hits_a, dtype=np.uint32).reshape(-1)
+        b = np.ascontiguousarray(hits_b, dtype=np.uint32).reshape(-1)
+        na, nb = int(n_a), int(n_b)
+        if a.size < hits_words(na, n_windows, int(levels) - 1) or b.size < hits_words(nb, n_windows, int(levels) - 1):
+            raise ValueError("hit matrix smaller than (levels, n_windows, ceil(n / 32))")
+        words = cross_cooccurrence_words(na, nb, levels)
+        out = np.full(max(words, 1), 0xFFFFFFFF, dtype=np.uint32)
+        one = np.zeros(1, np.uint32)
+        check(self._L.ac_hit_cross_cooccurrence(self._h, _ptr(a if a.size else one, ctypes.c_uint32), na,
+                                                _ptr(b if b.size else one, ctypes.c_uint32), nb, int(n_windows),
+                                                int(levels), _ptr(out, ctypes.c_uint32)), self._h)
+        return out[:words].reshape(int(levels), na, nb)
 
     def exact_path(self) -> int:
         """ac_exact_path: 1 partitioned, 0 hash table, -1 no exact count yet."""

@@ -20,6 +20,13 @@
 //   --cooccurrence  beside every <out>_<run>.<end> file a <out>_<run>.<end>.cooc file: per k-mer, in the same
 //                   order, for every k-mer of the file how many sampled windows hold the two together within
 //                   E edits (two of the reference's bitfields at once; ac_hit_cooccurrence)
+//   --paired-sample one sample of reads a run for both ends: window i of the start sample and window i of the end
+//                   sample come from the same read (the reference, approx_counter.cpp:867, shuffles once an end)
+//   --cross-cooccurrence
+//                   a <out>_<run>.cross file: per k-mer of the .start file, in its order, for every k-mer of the
+//                   .end file in its order how many sampled reads hold the first in their start window and the
+//                   second in their end window, both within E edits (ac_hit_cross_cooccurrence); needs
+//                   --paired-sample
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -102,6 +109,15 @@ const Opt OPTS[] = {
      "k-mer and, for every k-mer of the main file in the same order, the number of sampled windows holding both "
      "within max-errors edits (entry i of line i is the last column of its .levels line). Same needs as --levels, "
      "with which and with --positions it can be combined."},
+    {"", "paired-sample", Kind::Flag,
+     "[MI355X build] draw one sample of reads per run for both ends: window i of the start sample and window i of "
+     "the end sample come from the same read (by default each end is sampled on its own, as the reference does). "
+     "Cannot be combined with -se."},
+    {"", "cross-cooccurrence", Kind::Flag,
+     "[MI355X build] also write <out>_<run>.cross: one line per k-mer of the .start file, in its order, the k-mer "
+     "and, for every k-mer of the .end file in its order, the number of sampled reads holding the first in their "
+     "start window and the second in their end window, both within max-errors edits. Needs --paired-sample; "
+     "otherwise the needs of --levels, with which and with --positions and --cooccurrence it can be combined."},
     {"", "host-exact", Kind::Flag,
      "[MI355X build] the reference's host stages: whole reads in memory, exact k-mer count on the CPU"},
     {"", "dump-sample", Kind::String,
@@ -325,6 +341,30 @@ bool export_cooccurrence(const pair_vector& ranked, const std::vector<uint64_t>&
     return std::fclose(f) == 0;
 }
 
+// --cross-cooccurrence: one line per k-mer of the .start file (`rows`), the k-mer and one count per k-mer of the
+// .end file (`cols`) in its order -- `cross` is the n_a x n_b result of ac_hit_cross_cooccurrence over the two
+// jobs' top level planes, candidates kmers_a[a] and kmers_b[b], permuted here into the files' orders.
+bool export_cross(const pair_vector& rows, const pair_vector& cols, const std::vector<uint64_t>& kmers_a,
+                  const std::vector<uint64_t>& kmers_b, const std::vector<uint32_t>& cross, uint32_t k, const std::string& path) {
+    const size_t nb = kmers_b.size();
+    std::map<uint64_t, uint32_t> index_a, index_b;  // (the exact count's k-mers are distinct)
+    for (uint32_t c = 0; c < kmers_a.size(); ++c) index_a.emplace(kmers_a[c], c);
+    for (uint32_t c = 0; c < nb; ++c) index_b.emplace(kmers_b[c], c);
+    std::vector<uint32_t> order_b;
+    for (const auto& kv : cols) order_b.push_back(index_b.at(kv.first));
+    std::FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) return false;
+    std::string line;
+    for (const auto& kv : rows) {
+        const size_t a = index_a.at(kv.first);
+        line = int2dna(kv.first, k);
+        for (const uint32_t b : order_b) line += '\t' + std::to_string(cross[a * nb + b]);
+        line += '\n';
+        std::fwrite(line.data(), 1, line.size(), f);
+    }
+    return std::fclose(f) == 0;
+}
+
 void open_devices(Devices& dev, uint64_t n_gpus, uint64_t max_errors) {
     if (dev.ctx) return;
     if (n_gpus < 1) n_gpus = 1;
@@ -415,6 +455,8 @@ int main(int argc, char const** argv) {
     const bool levels = args.val.count("levels") > 0;
     const bool positions = args.val.count("positions") > 0;
     const bool cooccurrence = args.val.count("cooccurrence") > 0;
+    const bool paired = args.val.count("paired-sample") > 0;
+    const bool cross = args.val.count("cross-cooccurrence") > 0;
     std::string dump_sample;
     get_option(args, "dump-sample", dump_sample);
     const std::string input_file = args.input;
@@ -451,13 +493,29 @@ int main(int argc, char const** argv) {
             return 1;
         }
     }
+    // --paired-sample pairs the two ends; --cross-cooccurrence pairs rows of the two ends' hit matrices
+    if (paired && skip_end) {
+        std::cerr << error_pref << "--paired-sample cannot be combined with -se / --skip_end: there is no second end to pair"
+                  << std::endl;
+        return 1;
+    }
+    if (cross && !paired) {
+        std::cerr << error_pref
+                  << "--cross-cooccurrence needs --paired-sample: sampled on their own, the two ends' rows would be "
+                     "different reads"
+                  << std::endl;
+        return 1;
+    }
     // --levels: the hit levels come from the same kernel family under the same constraints
     // (ac_window_hits_samples); what only the sample can tell -- read ends of unequal length -- the
     // library refuses when the count is asked for.
     // --positions: the same kernels' sibling family, the same constraints and messages.
-    // --cooccurrence: a reduction of the same hit matrix, so the same again.
-    for (const char* flag : {"--levels", "--positions", "--cooccurrence"}) {
-        if (!(flag[2] == 'l' ? levels : flag[2] == 'p' ? positions : cooccurrence)) continue;
+    // --cooccurrence, --cross-cooccurrence: reductions of the same hit matrices, so the same again.
+    const std::pair<const char*, bool> hit_flags[] = {
+        {"--levels", levels}, {"--positions", positions}, {"--cooccurrence", cooccurrence}, {"--cross-cooccurrence", cross}};
+    for (const auto& hf : hit_flags) {
+        const char* flag = hf.first;
+        if (!hf.second) continue;
         const char* why = !(k == 16 || (k >= 18 && k <= 32)) ? " needs a kmer size (-k) of 16 or 18 to 32"
                           : sl > 255                         ? " needs a sampling length (-sl) of at most 255"
                           : n_gpus > 1                       ? " needs one GPU (-g 1)"
@@ -552,12 +610,15 @@ int main(int argc, char const** argv) {
             std::vector<uint32_t*> pos_p(pending.size());
             // --cooccurrence: the hits call as well, then the top level plane's co-occurrence
             std::vector<std::vector<uint32_t>> cooc(pending.size());
+            // --cross-cooccurrence: the hits call as well, then the two ends' top level planes against each other
+            const bool do_cross = cross && pending.size() == 2;
+            std::vector<uint32_t> cross_m;
             try {
                 devices();
                 const bool on_device = !host_exact && dev.shards == 1;  // the samples uploaded for the exact count
                 for (size_t e = 0; e < pending.size(); ++e)
                     jobs[e].sample = on_device ? pending[e].dsample : view(pending[e].img);
-                if (levels || positions || cooccurrence)
+                if (levels || positions || cooccurrence || cross)
                     for (size_t e = 0; e < pending.size(); ++e) {
                         hits[e].assign((size_t)ac_window_hits_words(jobs[e].n_kmers, jobs[e].sample.n_windows,
                                                                     (uint32_t)max_errors) + 1, 0u);
@@ -570,7 +631,7 @@ int main(int argc, char const** argv) {
                 const ac_status st =
                     positions   ? ac_window_positions_samples(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size(),
                                                               hits_p.data(), pos_p.data())
-                    : levels || cooccurrence
+                    : levels || cooccurrence || cross
                         ? ac_window_hits_samples(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size(), hits_p.data())
                     : on_device ? ac_error_count_samples(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size())
                                 : ac_error_count_images(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size());
@@ -584,10 +645,22 @@ int main(int argc, char const** argv) {
                         if (ac_hit_cooccurrence(dev.ctx, top, n, nw, 1u, cooc[e].data()) != AC_OK)
                             throw std::runtime_error(ac_last_error(dev.ctx));
                     }
+                if (do_cross) {
+                    const uint32_t na = jobs[0].n_kmers, nb = jobs[1].n_kmers, nw = jobs[0].sample.n_windows;
+                    if (jobs[1].sample.n_windows != nw)
+                        throw std::runtime_error("--cross-cooccurrence: the two ends hold " + std::to_string(nw) + " and " +
+                                                 std::to_string(jobs[1].sample.n_windows) + " windows, not the same reads");
+                    cross_m.assign((size_t)ac_hit_cross_cooccurrence_words(na, nb, 1) + 1, 0u);
+                    const uint32_t* top_a = hits[0].data() + (size_t)max_errors * (size_t)ac_window_hits_words(na, nw, 0u);
+                    const uint32_t* top_b = hits[1].data() + (size_t)max_errors * (size_t)ac_window_hits_words(nb, nw, 0u);
+                    if (ac_hit_cross_cooccurrence(dev.ctx, top_a, na, top_b, nb, nw, 1u, cross_m.data()) != AC_OK)
+                        throw std::runtime_error(ac_last_error(dev.ctx));
+                }
             } catch (const std::exception& e) {
                 std::cerr << error_pref << "approximate count failed: " << e.what() << std::endl;
                 return false;
             }
+            std::vector<pair_vector> ranked(pending.size());
             for (size_t e = 0; e < pending.size(); ++e) {
                 pair_vector error_counter(km[e].size());
                 for (size_t i = 0; i < km[e].size(); ++i) error_counter[i] = {km[e][i], ct[e][i]};
@@ -619,10 +692,31 @@ int main(int argc, char const** argv) {
                     return false;
                 }
                 if (mr_v > 0) print("Done", tab_level);
+                ranked[e] = std::move(sorted_error_count);
+            }
+            if (do_cross) {
+                const std::string path = output + run_suffix + ".cross";
+                if (!export_cross(ranked[0], ranked[1], km[0], km[1], cross_m, (uint32_t)k, path)) {
+                    std::cerr << error_pref + "Failed to export the cross co-occurrence" << std::endl;
+                    std::cerr << "Path: " << path << std::endl;
+                    return false;
+                }
             }
             pending.clear();
             return true;
         };
+        // --paired-sample: one draw for both ends, before the first
+        std::pair<PackedImage, PackedImage> pair_img;
+        std::pair<SeqSet, SeqSet> pair_seq;
+        if (paired) {
+            if (host_exact) {
+                pair_seq = sample_sequences_pair(seqs, sn, sl, rng);
+                pair_img = {pack_sample(pair_seq.first, 0, pair_seq.first.size()),
+                            pack_sample(pair_seq.second, 0, pair_seq.second.size())};
+            } else {
+                pair_img = sample_windows_pair(store, sn, rng);
+            }
+        }
         for (const std::string which_end : {"start", "end"}) {
             if (v > 0) print("Working on sequence " + which_end + ".", tab_level - 1);
             if (mr_v > 0) print("Sampling", tab_level);
@@ -630,7 +724,10 @@ int main(int argc, char const** argv) {
             End cur;
             cur.which = which_end;
             SeqSet sample;
-            if (host_exact) {
+            if (paired) {
+                sample = std::move(bottom ? pair_seq.second : pair_seq.first);
+                cur.img = std::move(bottom ? pair_img.second : pair_img.first);
+            } else if (host_exact) {
                 sample = sample_sequences(seqs, sn, sl, bottom, rng);
                 cur.img = pack_sample(sample, 0, sample.size());
             } else {

@@ -396,19 +396,14 @@ void read_windows(const std::string& path, uint64_t cut, WindowStore& ws, unsign
     for_each_record(path, WindowPacker{ws});
 }
 
-PackedImage sample_windows(const WindowStore& ws, uint64_t nb_sample, bool bot, std::mt19937& rng) {
-    std::vector<int> vec(ws.size());
-    std::iota(vec.begin(), vec.end(), 0);
-    std::shuffle(vec.begin(), vec.end(), rng);  // the same draws as sample_sequences
+namespace {
+
+// The window image of the stored pairs `picked`, in that order: their prefixes, or their suffixes (`bot`).
+PackedImage image_of_picks(const WindowStore& ws, const std::vector<uint32_t>& picked, bool bot) {
     const uint64_t pair = ws.prefix_bases + ws.suffix_bases;
     const uint64_t wbases = bot ? ws.suffix_bases : ws.prefix_bases;
     const uint64_t off = bot ? ws.prefix_bases : 0;
     const uint32_t wlen = (uint32_t)(bot ? ws.cut + 1 : ws.cut);
-    std::vector<uint32_t> picked;
-    for (size_t i = 0; picked.size() < nb_sample && i < vec.size(); ++i) {
-        const size_t id = (size_t)vec[i];
-        if (ws.slot[id] != ~0u && (!bot || ws.length[id] >= ws.cut + 1)) picked.push_back(ws.slot[id]);
-    }
     PackedImage p;
     p.n_bases = std::max<uint64_t>(32, wbases * picked.size());
     p.codes.assign(p.n_bases / 16, 0u);
@@ -422,6 +417,32 @@ PackedImage sample_windows(const WindowStore& ws, uint64_t nb_sample, bool bot, 
         std::memcpy(&p.nmask[dst / 32], &ws.nmask[src / 32], wbases / 32 * sizeof(uint32_t));
     }
     return p;
+}
+
+}  // namespace
+
+PackedImage sample_windows(const WindowStore& ws, uint64_t nb_sample, bool bot, std::mt19937& rng) {
+    std::vector<int> vec(ws.size());
+    std::iota(vec.begin(), vec.end(), 0);
+    std::shuffle(vec.begin(), vec.end(), rng);  // the same draws as sample_sequences
+    std::vector<uint32_t> picked;
+    for (size_t i = 0; picked.size() < nb_sample && i < vec.size(); ++i) {
+        const size_t id = (size_t)vec[i];
+        if (ws.slot[id] != ~0u && (!bot || ws.length[id] >= ws.cut + 1)) picked.push_back(ws.slot[id]);
+    }
+    return image_of_picks(ws, picked, bot);
+}
+
+std::pair<PackedImage, PackedImage> sample_windows_pair(const WindowStore& ws, uint64_t nb_sample, std::mt19937& rng) {
+    std::vector<int> vec(ws.size());
+    std::iota(vec.begin(), vec.end(), 0);
+    std::shuffle(vec.begin(), vec.end(), rng);  // one shuffle for both ends
+    std::vector<uint32_t> picked;
+    for (size_t i = 0; picked.size() < nb_sample && i < vec.size(); ++i) {
+        const size_t id = (size_t)vec[i];
+        if (ws.slot[id] != ~0u && ws.length[id] >= ws.cut + 1) picked.push_back(ws.slot[id]);
+    }
+    return {image_of_picks(ws, picked, false), image_of_picks(ws, picked, true)};
 }
 
 PackedImage pack_sample(const SeqSet& s, size_t lo, size_t hi) {
@@ -503,6 +524,26 @@ SeqSet sample_sequences(const SeqSet& seqs, uint64_t nb_sample, uint64_t cut, bo
             } else {
                 sample.add(seqs.seq(id), (uint32_t)cur_cut);
             }
+            ++nb_seq;
+        }
+    }
+    return sample;
+}
+
+std::pair<SeqSet, SeqSet> sample_sequences_pair(const SeqSet& seqs, uint64_t nb_sample, uint64_t cut, std::mt19937& rng) {
+    std::pair<SeqSet, SeqSet> sample;
+    std::vector<int> vec(seqs.size());
+    std::iota(vec.begin(), vec.end(), 0);
+    std::shuffle(vec.begin(), vec.end(), rng);  // one shuffle for both ends
+    uint64_t nb_seq = 0;
+    for (size_t i = 0; nb_seq < nb_sample && i < vec.size(); ++i) {
+        const size_t id = (size_t)vec[i];
+        const uint64_t len = seqs.length[id];
+        const uint64_t cur_cut = std::min<uint64_t>(len, cut);
+        if (len >= cut * 2 && len >= cur_cut + 1) {  // sample_sequences' eligibility for the end window
+            const uint64_t from = len - 1 - cur_cut;
+            sample.first.add(seqs.seq(id), (uint32_t)cur_cut);
+            sample.second.add(seqs.seq(id) + from, (uint32_t)(len - from));
             ++nb_seq;
         }
     }

@@ -97,10 +97,20 @@ void read_windows(const std::string& path, uint64_t cut, WindowStore& out, unsig
 // (identical to pack_sample(sample_sequences(...)) word for word).
 PackedImage sample_windows(const WindowStore& ws, uint64_t nb_sample, bool bot, std::mt19937& rng);
 
+// One sample for both ends: a single shuffle of the read indices, walked for up to nb_sample reads eligible
+// at both ends (stored, and of length >= cut + 1).  Returns {start image, end image}: window i of both
+// comes from the same read, in pick order, and each image is word for word what sample_windows builds from
+// that pick list.  (sampleSequences, approx_counter.cpp:867, is called once an end with a fresh shuffle, so
+// the reference's two samples are different reads.)
+std::pair<PackedImage, PackedImage> sample_windows_pair(const WindowStore& ws, uint64_t nb_sample, std::mt19937& rng);
+
 // sampleSequences (approx_counter.cpp:415-476): walks a shuffled permutation
 // of the reads and keeps, for up to nb_sample reads of length >= 2*cut, the
 // first `cut` bases (start) or the last cut+1 bases (end, `bot`).
 SeqSet sample_sequences(const SeqSet& seqs, uint64_t nb_sample, uint64_t cut, bool bot, std::mt19937& rng);
+// The same with one shuffle for both ends: {starts, ends} of up to nb_sample reads that sample_sequences
+// could pick for the end window, sequence i of both from the same read.
+std::pair<SeqSet, SeqSet> sample_sequences_pair(const SeqSet& seqs, uint64_t nb_sample, uint64_t cut, std::mt19937& rng);
 
 // count_kmers (approx_counter.cpp:487-519): exact counts of the k-mers of the
 // sample holding no N, passing the low-complexity filter and not forbidden.

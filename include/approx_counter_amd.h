@@ -650,6 +650,39 @@ ac_status ac_hit_cooccurrence(ac_ctx* ctx, const uint32_t* hits_host, uint32_t n
 ac_status ac_hit_window_counts_device(ac_ctx* ctx, const uint32_t* hits, uint32_t n_kmers, uint32_t n_windows,
                                       uint32_t levels, uint32_t* window_counts, void* hip_stream);
 
+/*
+ * Cross co-occurrence (additive exports of ABI 8): the same reduction over two
+ * hit matrices A (n_a candidates) and B (n_b) that share their windows -- row w
+ * of both is the same read, as the paired sample of the command line
+ * (--paired-sample) makes a run's start and end windows.  Both are in the layout
+ * above over the same n_windows, `levels` planes each.
+ *   ac_hit_cross_cooccurrence_words    u32 words of a result: levels * n_a * n_b
+ *                                      (64-bit)
+ *   ac_hit_cross_cooccurrence_device   cross[(e * n_a + a) * n_b + b] = the
+ *                                      windows whose row of A's plane e has bit a
+ *                                      and whose row of B's plane e has bit b;
+ *                                      u32 values, 64-bit indices, stray bits
+ *                                      ignored, every word of the result written.
+ *                                      To pair plane d of A with plane d' of B
+ *                                      pass the planes' offsets with levels = 1;
+ *                                      A and B may be the same matrix.  Device
+ *                                      memory; asynchronous on hip_stream.
+ *   ac_hit_cross_cooccurrence          the same over host buffers; synchronous.
+ * Refused with AC_ERR_INVALID before anything is enqueued: a NULL context,
+ * levels outside 1..4, a NULL result when n_a and n_b are both > 0, a NULL
+ * hits_a or hits_b when n_a, n_b and n_windows are all > 0.  n_windows = 0
+ * writes zeros; n_a = 0 or n_b = 0 is no work.  Any context, k, budget and
+ * AC_BITSLICE; an ac_create_multi context uses its first device.  The scratch
+ * is the co-occurrence call's (both matrices' planes transposed: grown on demand,
+ * AC_ERR_NOMEM if it cannot be, and stream-ordered with that call).
+ */
+uint64_t ac_hit_cross_cooccurrence_words(uint32_t n_a, uint32_t n_b, uint32_t levels);
+ac_status ac_hit_cross_cooccurrence_device(ac_ctx* ctx, const uint32_t* hits_a, uint32_t n_a, const uint32_t* hits_b,
+                                           uint32_t n_b, uint32_t n_windows, uint32_t levels, uint32_t* cross,
+                                           void* hip_stream);
+ac_status ac_hit_cross_cooccurrence(ac_ctx* ctx, const uint32_t* hits_a_host, uint32_t n_a, const uint32_t* hits_b_host,
+                                    uint32_t n_b, uint32_t n_windows, uint32_t levels, uint32_t* cross_host);
+
 #ifdef __cplusplus
 }
 #endif

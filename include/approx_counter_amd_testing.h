@@ -53,6 +53,12 @@ int ac_testing_last_count_kernel(ac_ctx* ctx);
 ac_status ac_testing_hit_cooccurrence_stages(ac_ctx* ctx, const uint32_t* hits, uint32_t n_kmers, uint32_t n_windows,
                                              uint32_t levels, uint32_t* cooc, uint32_t stages, void* hip_stream);
 
+/* ac_hit_cross_cooccurrence_device in steps, likewise (tools/kernel_run.py --cross): stages 1 = only the two
+ * matrices' transpositions, 2 = only the product from the scratch, 3 = both. */
+ac_status ac_testing_hit_cross_stages(ac_ctx* ctx, const uint32_t* hits_a, uint32_t n_a, const uint32_t* hits_b, uint32_t n_b,
+                                      uint32_t n_windows, uint32_t levels, uint32_t* cross, uint32_t stages,
+                                      void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

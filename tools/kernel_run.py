@@ -22,6 +22,10 @@ positions"); --profile then times ac_hit_position_profile_device over the first 
 resident matrix (ac_hit_cooccurrence_device, DESIGN.md 4e "Co-occurrence"): the transposition and the product on
 their own (ac_testing_hit_cooccurrence_stages) and the whole call, beside the level counter on the same plane and
 the op model n (n + 1) / 2 x ceil(W / 32) x 2 lane-ops against bench.py's VALU peak.
+--cross (with --hits or --positions) times the cross co-occurrence of the first two segments' top level planes
+(ac_hit_cross_cooccurrence_device, DESIGN.md 4e "Cross co-occurrence"; the segments must hold the same number of
+windows): the two transpositions and the cross product on their own (ac_testing_hit_cross_stages) and the whole
+call, beside the Gram call's stages on the first segment in the same session, and the product times per tile.
 --staged --hits / --positions run the staged hits kernels (ac_window_hits_jobs_submit, DESIGN.md 4e "Hits from the
 jobs stage") on input sent ahead; --staged --time the staged counting kernel the same way, to set them against.
 """
@@ -59,6 +63,9 @@ def main():
     ap.add_argument("--cooc", action="store_true",
                     help="with --hits / --positions: also time ac_hit_cooccurrence_device over the first segment's top "
                          "level plane: transposition, product and the whole call")
+    ap.add_argument("--cross", action="store_true",
+                    help="with --hits / --positions: also time ac_hit_cross_cooccurrence_device over the first two "
+                         "segments' top level planes: transpositions, product and the whole call, beside the Gram call")
     a = ap.parse_args()
     a.hits = a.hits or a.positions
     import torch
@@ -184,6 +191,48 @@ def main():
                   + ", ".join(f"{k} {v:.4f} ms" for k, v in ms.items())
                   + f" per call; op model {ops:.3e} lane-ops = {ops / bench.VALU_PEAK_OPS * 1e3:.4f} ms at the VALU peak, "
                   f"{ops / bench.VALU_PEAK_OPS * 1e3 / ms['product'] * 100:.1f} % of the product's time")
+        if a.hits and a.cross:
+            import ctypes
+
+            from approx_counter_amd import _lib
+
+            sa, sb = segs[0], segs[1]
+            na, nb, nw, E = sa.n_kmers, sb.n_kmers, sa.n_windows, a.max_errors
+            if sb.n_windows != nw:
+                sys.exit(f"--cross: the two segments hold {nw} and {sb.n_windows} windows; it needs equal counts")
+            top_a = hits[0][E * nw * ((na + 31) // 32):]
+            top_b = hits[1][E * nw * ((nb + 31) // 32):]
+            out = torch.empty(max(na * nb, 1), dtype=torch.int32, device="cuda")
+            gram = torch.empty(max(na * na, 1), dtype=torch.int32, device="cuda")
+            p = lambda t: ctypes.cast(ctypes.c_void_p(t.data_ptr()), _lib.p32)  # noqa: E731
+            L, h = c._L, c.handle
+            legs = [(f"cross {name}", lambda st: L.ac_testing_hit_cross_stages(h, p(top_a), na, p(top_b), nb, nw, 1, p(out), st, None), st)
+                    for name, st in (("transpositions", 1), ("product", 2), ("both", 3))]
+            legs += [(f"gram {name}", lambda st: L.ac_testing_hit_cooccurrence_stages(h, p(top_a), na, nw, 1, p(gram), st, None), st)
+                     for name, st in (("transposition", 1), ("product", 2), ("both", 3))]
+            ms = {}
+            for name, call, st in legs:  # (each leg's stage 2 reads the scratch its own stage 1 filled just before)
+                for i in range(a.warmup + a.launches):
+                    if i == a.warmup:
+                        t0.record()
+                    _lib.check(call(st), h)
+                t1.record()
+                torch.cuda.synchronize()
+                ms[name] = t0.elapsed_time(t1) / a.launches
+            g = gram[: na * na].view(na, na).clone()
+            _lib.check(L.ac_hit_cross_cooccurrence_device(h, p(top_a), na, p(top_a), na, nw, 1, p(gram), None), h)
+            torch.cuda.synchronize()
+            assert (gram[: na * na].view(na, na) == g).all(), "cross(A, A) is not the Gram product"
+            lc = c.hit_level_counts(top_b, nb, nw, 1)
+            cx = out[: na * nb].view(na, nb)
+            assert (cx <= lc[0][None, :]).all(), "a cross count exceeds its column's level count"
+            ta, tb = (na + 63) // 64, (nb + 63) // 64
+            tiles, pairs = ta * tb, ta * (ta + 1) // 2
+            per_c, per_g = ms["cross product"] / tiles, ms["gram product"] / pairs
+            print(f"cross co-occurrence of planes {E} ({na} x {nb} k-mers, {nw} windows, {4 * na * nb} bytes out): "
+                  + ", ".join(f"{k} {v:.4f} ms" for k, v in ms.items())
+                  + f" per call; cross product {per_c * 1e3:.4f} us per tile ({tiles} tiles), gram product "
+                  f"{per_g * 1e3:.4f} us per tile pair ({pairs} pairs), ratio {per_c / per_g:.3f}")
         if a.positions and a.profile:
             s0 = segs[0]
             for i in range(a.warmup + a.launches):
