@@ -61,29 +61,13 @@ $(OBJDIR)/wm_count.o: $(WM_SRC) $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) -c $< -o $@
 
-# the bit-sliced kernels for an edit budget of 3: the same frame and body, a translation unit of its own
-# (it compiles beside wm_count.o)
-$(OBJDIR)/bs3_count.o: $(CSRC)/bs3_count.hip $(CSRC)/stage_dev.inc $(CSRC)/count_frame.inc $(CSRC)/bs_count.inc $(HDRS)
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) -c $< -o $@
+# the other families of the bit-sliced kernels (E = 3; hits; hits and positions; the staged forms of those
+# two), with the reduction kernels that live beside them: the same frame and body through bs_family.inc,
+# each a translation unit of its own (they compile beside wm_count.o)
+BS_UNITS := bs3_count bsh_count bsp_count bshs_count bsps_count
+BS_INCS := $(CSRC)/bs_family.inc $(CSRC)/stage_dev.inc $(CSRC)/count_frame.inc $(CSRC)/bs_count.inc
 
-# the hits-writing family of the bit-sliced kernels (and the level-count kernel): again the same frame and
-# body in a translation unit of its own
-$(OBJDIR)/bsh_count.o: $(CSRC)/bsh_count.hip $(CSRC)/stage_dev.inc $(CSRC)/count_frame.inc $(CSRC)/bs_count.inc $(HDRS)
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) -c $< -o $@
-
-# the hits-and-positions family (and the position-profile kernel), likewise
-$(OBJDIR)/bsp_count.o: $(CSRC)/bsp_count.hip $(CSRC)/stage_dev.inc $(CSRC)/count_frame.inc $(CSRC)/bs_count.inc $(HDRS)
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) -c $< -o $@
-
-# the staged forms of the two families above (hits from the jobs stage), each a translation unit of its own
-$(OBJDIR)/bshs_count.o: $(CSRC)/bshs_count.hip $(CSRC)/stage_dev.inc $(CSRC)/count_frame.inc $(CSRC)/bs_count.inc $(HDRS)
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) -c $< -o $@
-
-$(OBJDIR)/bsps_count.o: $(CSRC)/bsps_count.hip $(CSRC)/stage_dev.inc $(CSRC)/count_frame.inc $(CSRC)/bs_count.inc $(HDRS)
+$(BS_UNITS:%=$(OBJDIR)/%.o): $(OBJDIR)/%.o: $(CSRC)/%.hip $(BS_INCS) $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) -c $< -o $@
 
@@ -105,7 +89,7 @@ $(HOSTONLY:%=$(OBJDIR)/%.o): $(OBJDIR)/%.o: $(CSRC)/%.cpp $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(CXX) $(HOST_CXXFLAGS) $(HIP_HOST) $(INCS) -c $< -o $@
 
-$(LIB): $(OBJDIR)/wm_count.o $(OBJDIR)/bs3_count.o $(OBJDIR)/bsh_count.o $(OBJDIR)/bsp_count.o $(OBJDIR)/bshs_count.o $(OBJDIR)/bsps_count.o $(OBJDIR)/hit_cooc.o $(OBJDIR)/hit_cross.o $(OBJDIR)/exact_count.o $(OBJDIR)/jobs_stage.o $(CAPI:%=$(OBJDIR)/%.o) $(HOSTONLY:%=$(OBJDIR)/%.o)
+$(LIB): $(OBJDIR)/wm_count.o $(BS_UNITS:%=$(OBJDIR)/%.o) $(OBJDIR)/hit_cooc.o $(OBJDIR)/hit_cross.o $(OBJDIR)/exact_count.o $(OBJDIR)/jobs_stage.o $(CAPI:%=$(OBJDIR)/%.o) $(HOSTONLY:%=$(OBJDIR)/%.o)
 	@mkdir -p $(dir $@)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -pthread
 
@@ -121,16 +105,17 @@ $(CLI): $(HOSTDIR)/adaptfinder.cpp $(HOST_SRC) $(HOST_HDRS) $(CSRC)/hit_levels.h
 oracle:
 	$(MAKE) -s -C oracle
 
-asm: $(WM_SRC) $(HDRS)
+# the device assembly of every kernel unit, into build/asm
+ASM_WM := wm_count $(BS_UNITS)
+asm: $(ASM_WM:%=build/asm/%.s) build/asm/hit_cooc.s build/asm/hit_cross.s
+
+$(ASM_WM:%=build/asm/%.s): build/asm/%.s: $(CSRC)/%.hip $(WM_SRC) $(BS_INCS) $(HDRS)
 	@mkdir -p build/asm
-	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) --cuda-device-only -S $< -o build/asm/wm_count.s
-	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) --cuda-device-only -S $(CSRC)/bs3_count.hip -o build/asm/bs3_count.s
-	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) --cuda-device-only -S $(CSRC)/bsh_count.hip -o build/asm/bsh_count.s
-	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) --cuda-device-only -S $(CSRC)/bsp_count.hip -o build/asm/bsp_count.s
-	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) --cuda-device-only -S $(CSRC)/bshs_count.hip -o build/asm/bshs_count.s
-	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) --cuda-device-only -S $(CSRC)/bsps_count.hip -o build/asm/bsps_count.s
-	$(HIPCC) $(HIPFLAGS) $(INCS) --cuda-device-only -S $(CSRC)/hit_cooc.hip -o build/asm/hit_cooc.s
-	$(HIPCC) $(HIPFLAGS) $(INCS) --cuda-device-only -S $(CSRC)/hit_cross.hip -o build/asm/hit_cross.s
+	$(HIPCC) $(HIPFLAGS) $(WM_FLAGS) $(INCS) --cuda-device-only -S $< -o $@
+
+build/asm/%.s: $(CSRC)/%.hip $(HDRS)
+	@mkdir -p build/asm
+	$(HIPCC) $(HIPFLAGS) $(INCS) --cuda-device-only -S $< -o $@
 
 clean:
 	rm -rf build $(LIBDIR) $(BINDIR) oracle/_build

@@ -1,8 +1,8 @@
 // bs_count.inc -- the bit-sliced count kernel's body (DESIGN.md §4e), included by wm_count.hip (three NFA
-// rows: edit budgets 0..2), by bs3_count.hip (four rows: budget 3), by bsh_count.hip (either, and the
-// windows' hit words stored beside the counts), by bsp_count.hip (either, the hit words and the match end
-// positions) and by bshs_count.hip / bsps_count.hip (the staged forms of those two) inside their anonymous
-// namespaces:
+// rows: edit budgets 0..2) and, through bs_family.inc, by bs3_count.hip (four rows: budget 3), by
+// bsh_count.hip (either, and the windows' hit words stored beside the counts), by bsp_count.hip (either, the
+// hit words and the match end positions) and by bshs_count.hip / bsps_count.hip (the staged forms of those
+// two) inside their anonymous namespaces:
 // the NFA's place in the frame of count_frame.inc (deal, staged prologue,
 // sub-queues, gate, count hand-off -- the word-parallel kernel's), with another mapping of a wave
 // onto the work.
@@ -25,7 +25,7 @@
 // one address).  Characters 4..7 (an N base, whatever its code bits) are all ones, as are the bits
 // of candidate slots past n_kmers.
 // Only equal-window launches (every live segment has ulen in 1..256) with K in AC_BS_K_LIST; the
-// residency of an instantiation is bs_waves_per_simd(K) (wm_count.h).
+// residency of an instantiation is bs_waves_per_simd(family, K) (wm_count.h).
 constexpr uint32_t BS_LWMAX = BS_GROUP / 32u;       // lanes per window of a full group
 constexpr uint32_t BS_ROW = BS_LWMAX * 16u;         // bytes of one (character, quad) table row
 

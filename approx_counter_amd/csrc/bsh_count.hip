@@ -2,9 +2,7 @@
 // bs_count.inc's body with HITS on, which beside the counts stores every window's hit word of each level
 // 0..E -- what the reference keeps per read in tcount[errors][read] (approx_counter.cpp:553-565) before
 // vectorSum collapses it (580-596).  One instantiation per k in AC_BS_K_LIST over three NFA rows (edit
-// budgets 0..2) and over four (budget 3), plain only: the staged forms are bshs_count.hip's.  A
-// translation unit of its own, like bs3_count.hip, so that the counting kernels' device compiles stay
-// what they were; wm_count.hip's dispatch (count_kernel) takes its kernels from bsh_kernel().
+// budgets 0..2) and over four (budget 3), plain only: the staged forms are bshs_count.hip's.
 // With it: the kernel that turns a hit matrix into per-level counts (hit_levels.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -21,34 +19,22 @@
 namespace acamd {
 namespace {
 
-constexpr int WAVES_PER_BLOCK = AC_WAVES_PER_BLOCK;
-// (the diagnostic stamps of wm_count.hip's -DAC_STAMPS builds are taken by the E = 2 kernels only)
-__device__ __forceinline__ void stamp(uint64_t, int) {}
-__device__ __forceinline__ void stage_stamp(uint32_t, int) {}
+#include "bs_family.inc"
 
-// (the frame also holds what only the word-parallel kernel calls)
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"
-#include "stage_dev.inc"
-#include "count_frame.inc"
-#pragma clang diagnostic pop
-#include "bs_count.inc"
+constexpr BsFamily family(int rows) { return BsFamily{false, BsOut::Hits, rows}; }
 
 }  // namespace
 
-// k = K, equal windows, R NFA rows (3: E = 0..2, 4: E = 3), counts and hits.  bsh_waves_per_simd waves per
-// SIMD, capped by the LDS allocation like bs_count_kernel.
+// k = K, equal windows, R NFA rows (3: E = 0..2, 4: E = 3), counts and hits, at its family's residency.
 template <int K, int R>
-__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, bsh_waves_per_simd(K, R == 4 ? 3 : 2)) void bsh_count_kernel(LaunchArgs a) {
-    constexpr int kBlocksPerCu = 4 * bsh_waves_per_simd(K, R == 4 ? 3 : 2) / WAVES_PER_BLOCK;
-    __shared__ BsLds<K> lds[(160 * 1024 / kBlocksPerCu) / sizeof(BsLds<K>)];
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, bs_waves_per_simd(family(R), K)) void bsh_count_kernel(LaunchArgs a) {
+    __shared__ BsLds<K> lds[(160 * 1024 / bs_blocks_per_cu(family(R), K)) / sizeof(BsLds<K>)];
     bs_body<K, false, R, true>(a, lds[0]);
 }
 
-void (*bsh_kernel(uint32_t k, uint32_t max_errors))(LaunchArgs) {
-    if (max_errors > 3u) return nullptr;
+CountKernel bsh_kernel(uint32_t k, BsFamily f) {
 #define AC_BS_PICK(KK) \
-    if (k == KK) return max_errors == 3u ? bsh_count_kernel<KK, 4> : bsh_count_kernel<KK, 3>;
+    if (k == KK) return f.rows == 4 ? bsh_count_kernel<KK, 4> : bsh_count_kernel<KK, 3>;
     AC_BS_K_LIST(AC_BS_PICK)
 #undef AC_BS_PICK
     return nullptr;

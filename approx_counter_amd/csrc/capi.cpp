@@ -64,8 +64,6 @@ ac_status grow(ac_ctx* ctx, void** buf, size_t* cap, size_t bytes) {
     return AC_OK;
 }
 
-static ac_status ensure(ac_ctx* ctx, int slot, size_t bytes) { return grow(ctx, &ctx->d_buf[slot], &ctx->d_cap[slot], bytes); }
-
 // Host -> device copy of n host arrays through the context's pinned staging
 // block.  Array i lands at offset off(i) = sum of the earlier sizes rounded up
 // to 256 B, in the staging block and in the device block `dst` alike.  The
@@ -258,8 +256,11 @@ ac_status ac_create(ac_ctx** out, int device) {
                 (void)acamd::resident_waves(P, st != 0, ctx->cu_count, &ctx->warm_resident[st][P]);
         // (the bit-sliced kernels' code with them: the k = 16 queries load the code object; another
         // k is queried at its first launch, so start-up does not grow with AC_BS_K_LIST)
-        for (int st = 0; st < 2; ++st)
-            (void)acamd::resident_waves_bs(16u, st != 0, ctx->cu_count, &ctx->warm_resident_bs[st][16]);
+        for (int st = 0; st < 2; ++st) {
+            const acamd::BsFamily counting = acamd::bs_family(st != 0, false, false, 2u);
+            (void)acamd::resident_waves_bs(counting, 16u, ctx->cu_count,
+                                           &ctx->warm_resident_bs[acamd::bs_family_index(counting)][16]);
+        }
         ac_ctx::Scratch& sc = ctx->sc[0];
         auto zeroed = [](void** p, size_t bytes) {
             if (hipMalloc(p, bytes) != hipSuccess) return false;
@@ -283,8 +284,8 @@ void ac_destroy(ac_ctx* ctx) {
     for (ac_ctx* p : ctx->peers) ac_destroy(p);
     (void)hipSetDevice(ctx->device);
     comm_destroy(ctx);
-    for (void* p : ctx->d_buf)
-        if (p) (void)hipFree(p);
+    if (ctx->d_kmers) (void)hipFree(ctx->d_kmers);
+    if (ctx->d_counts) (void)hipFree(ctx->d_counts);
     if (ctx->d_stage) (void)hipFree(ctx->d_stage);
     if (ctx->d_hits) (void)hipFree(ctx->d_hits);
     if (ctx->d_pos) (void)hipFree(ctx->d_pos);
@@ -321,20 +322,30 @@ void ac_destroy(ac_ctx* ctx) {
     delete ctx;
 }
 
+// The device entry points' window_len (NULL: the segments come with window descriptors), checked and copied
+// into ul: *ulen = ul, or NULL.
+static ac_status take_window_len(ac_ctx* ctx, const uint32_t* window_len, uint32_t n_segments, uint32_t (&ul)[AC_MAX_SEGS],
+                                 const uint32_t** ulen) {
+    *ulen = window_len ? ul : nullptr;
+    if (window_len)
+        for (uint32_t i = 0; i < n_segments; ++i) {
+            if (window_len[i] == AC_NO_ULEN) return fail(ctx, AC_ERR_INVALID, "window_len out of range");
+            ul[i] = window_len[i];
+        }
+    return AC_OK;
+}
+
 ac_status ac_error_count_device(ac_ctx* ctx, uint32_t k, const ac_segment* segments, uint32_t n_segments,
                                 const uint32_t* window_len, uint32_t flags, void* hip_stream) {
     if (!ctx) return fail(nullptr, AC_ERR_INVALID, "ctx is NULL");
     if (flags & ~AC_DEVICE_ACCUMULATE) return fail(ctx, AC_ERR_INVALID, "unknown flags");
     if (n_segments > AC_MAX_SEGS) return fail(ctx, AC_ERR_INVALID, "too many segments in one launch (max 4)");
     uint32_t ul[AC_MAX_SEGS];
-    if (window_len)
-        for (uint32_t i = 0; i < n_segments; ++i) {
-            if (window_len[i] == AC_NO_ULEN) return fail(ctx, AC_ERR_INVALID, "window_len out of range");
-            ul[i] = window_len[i];
-        }
+    CountLaunch rq(k, segments, n_segments, (hipStream_t)hip_stream);
+    if (ac_status st = take_window_len(ctx, window_len, n_segments, ul, &rq.ulen)) return st;
     AC_HIP(ctx, hipSetDevice(ctx->device));
-    return launch(ctx, k, segments, n_segments, (hipStream_t)hip_stream, !(flags & AC_DEVICE_ACCUMULATE), nullptr, 0,
-                  0, nullptr, window_len ? ul : nullptr);
+    rq.zero = !(flags & AC_DEVICE_ACCUMULATE);
+    return launch(ctx, rq);
 }
 
 }  // extern "C"
@@ -400,7 +411,9 @@ ac_status count_images_one(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, u
         coff += align256(sizeof(uint32_t) * jobs[j].n_kmers);
     }
     hipStream_t st = ctx->stream;
-    if (ac_status rc = launch(ctx, k, seg, n, st, true, (uint32_t*)(d + off_err))) return rc;
+    CountLaunch rq(k, seg, n, st);
+    rq.err = (uint32_t*)(d + off_err);
+    if (ac_status rc = launch(ctx, rq)) return rc;
     AC_HIP(ctx, hipMemcpyAsync(h + off_err, d + off_err, coff - off_err, hipMemcpyDeviceToHost, st));
     AC_HIP(ctx, hipStreamSynchronize(st));
     if (ac_status rc = device_error(ctx, *(const uint32_t*)(h + off_err))) return rc;
@@ -631,27 +644,30 @@ static ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* job
     }
     AC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    // every job's k-mers in one upload (d_buf[0]); uint32 counts in d_buf[5], one D2H
+    // every job's k-mers in one upload; uint32 counts, one D2H
     std::vector<uint64_t> km;
     km.reserve(total);
     for (uint32_t j = 0; j < n_jobs; ++j) km.insert(km.end(), jobs[j].kmers, jobs[j].kmers + jobs[j].n_kmers);
-    if (ac_status s2 = ensure(ctx, 0, sizeof(uint64_t) * total)) return s2;
-    if (ac_status s2 = ensure(ctx, 5, sizeof(uint32_t) * total)) return s2;
-    AC_HIP(ctx, hipMemcpyAsync(ctx->d_buf[0], km.data(), sizeof(uint64_t) * total, hipMemcpyHostToDevice, st));
+    if (ac_status s2 = grow(ctx, &ctx->d_kmers, &ctx->d_kmers_cap, sizeof(uint64_t) * total)) return s2;
+    if (ac_status s2 = grow(ctx, &ctx->d_counts, &ctx->d_counts_cap, sizeof(uint32_t) * total)) return s2;
+    AC_HIP(ctx, hipMemcpyAsync(ctx->d_kmers, km.data(), sizeof(uint64_t) * total, hipMemcpyHostToDevice, st));
     ac_segment seg[AC_MAX_JOBS];
     uint64_t base = 0;
     for (uint32_t j = 0; j < n_jobs; ++j) {
-        seg[j].kmers = (const uint64_t*)ctx->d_buf[0] + base;
+        seg[j].kmers = (const uint64_t*)ctx->d_kmers + base;
         seg[j].n_kmers = jobs[j].n_kmers;
         seg[j].sample = jobs[j].sample;
-        seg[j].counts = (uint32_t*)ctx->d_buf[5] + base;
+        seg[j].counts = (uint32_t*)ctx->d_counts + base;
         base += jobs[j].n_kmers;
     }
-    if (ac_status rc = launch(ctx, k, seg, n_jobs, st, true, nullptr, 0, 0, no_n, ulen, nullptr, nullptr,
-                              hits_host ? d_hits : nullptr, hits_host && pos_host ? d_pos : nullptr))
-        return rc;
+    CountLaunch rq(k, seg, n_jobs, st);
+    rq.no_n = no_n;
+    rq.ulen = ulen;
+    rq.hits = hits_host ? d_hits : nullptr;
+    rq.pos = hits_host && pos_host ? d_pos : nullptr;
+    if (ac_status rc = launch(ctx, rq)) return rc;
     ctx->h_counts.resize(total);
-    AC_HIP(ctx, hipMemcpyAsync(ctx->h_counts.data(), ctx->d_buf[5], sizeof(uint32_t) * total, hipMemcpyDeviceToHost, st));
+    AC_HIP(ctx, hipMemcpyAsync(ctx->h_counts.data(), ctx->d_counts, sizeof(uint32_t) * total, hipMemcpyDeviceToHost, st));
     if (hits_host)
         for (uint32_t j = 0; j < n_jobs; ++j)
             if (jobs[j].n_kmers && jobs[j].sample.n_windows)
@@ -685,15 +701,13 @@ static ac_status window_hits_device(ac_ctx* ctx, uint32_t k, const ac_segment* s
     if (n_segments && !hits) return fail(ctx, AC_ERR_INVALID, "window hits: hits is NULL");
     if (with_pos && n_segments && !pos) return fail(ctx, AC_ERR_INVALID, "window positions: pos is NULL");
     uint32_t ul[AC_MAX_SEGS];
-    if (window_len)
-        for (uint32_t i = 0; i < n_segments; ++i) {
-            if (window_len[i] == AC_NO_ULEN) return fail(ctx, AC_ERR_INVALID, "window_len out of range");
-            ul[i] = window_len[i];
-        }
+    CountLaunch rq(k, segments, n_segments, (hipStream_t)hip_stream);
+    if (ac_status st = take_window_len(ctx, window_len, n_segments, ul, &rq.ulen)) return st;
     static uint32_t* const none[AC_MAX_SEGS] = {};
     AC_HIP(ctx, hipSetDevice(ctx->device));
-    return launch(ctx, k, segments, n_segments, (hipStream_t)hip_stream, true, nullptr, 0, 0, nullptr,
-                  window_len ? ul : nullptr, nullptr, nullptr, hits ? hits : none, with_pos ? (pos ? pos : none) : nullptr);
+    rq.hits = hits ? hits : none;
+    rq.pos = with_pos ? (pos ? pos : none) : nullptr;
+    return launch(ctx, rq);
 }
 
 ac_status ac_window_hits_device(ac_ctx* ctx, uint32_t k, const ac_segment* segments, uint32_t n_segments,

@@ -38,9 +38,9 @@ void ensure_warm(ac_ctx* ctx) {
     for (int st = 0; st < 2; ++st)
         for (uint32_t P = 1; P <= AC_MAX_PACK; ++P)
             if (!ctx->resident[st][P]) ctx->resident[st][P] = ctx->warm_resident[st][P];
-    for (int st = 0; st < 2; ++st)
+    for (int f = 0; f < acamd::BS_FAMILIES; ++f)
         for (uint32_t kk = 0; kk <= 32; ++kk)
-            if (!ctx->resident_bs[st][kk]) ctx->resident_bs[st][kk] = ctx->warm_resident_bs[st][kk];
+            if (!ctx->resident_bs[f][kk]) ctx->resident_bs[f][kk] = ctx->warm_resident_bs[f][kk];
 }
 
 // Waves of a bit-sliced launch of `items` row items, of `resident` that fit at once: a
@@ -51,13 +51,9 @@ void ensure_warm(ac_ctx* ctx) {
 // That was measured at four waves per SIMD and holds for the kernels of that residency (k = 16) only:
 // the wider patterns' kernels, at 2-3 waves per SIMD, launch every resident workgroup.
 // AC_BS_WAVES_PCT (1..100) sets the share for every bit-sliced launch instead, for A/B runs.
-static uint64_t bs_launch_waves(uint32_t k, uint32_t max_errors, bool hits, bool pos, bool staged, uint64_t items,
-                                uint64_t resident) {
+static uint64_t bs_launch_waves(acamd::BsFamily family, uint32_t k, uint64_t items, uint64_t resident) {
     static const int pct = env_int("AC_BS_WAVES_PCT", 0);
-    const int e = max_errors == 3u ? 3 : 2;
-    const int per_simd = pos    ? (staged ? acamd::bsps_waves_per_simd((int)k, e) : acamd::bsp_waves_per_simd((int)k, e))
-                         : hits ? (staged ? acamd::bshs_waves_per_simd((int)k, e) : acamd::bsh_waves_per_simd((int)k, e))
-                                : acamd::bs_waves_per_simd((int)k, e);
+    const int per_simd = acamd::bs_waves_per_simd(family, (int)k);
     const bool three_of_four = per_simd == 4 && items > resident &&
                                4 * items <= 5 * resident;
     const uint64_t want = pct > 0 ? resident * (uint64_t)std::min(pct, 100) / 100
@@ -65,37 +61,17 @@ static uint64_t bs_launch_waves(uint32_t k, uint32_t max_errors, bool hits, bool
     return std::max<uint64_t>(AC_WAVES_PER_BLOCK, want / AC_WAVES_PER_BLOCK * AC_WAVES_PER_BLOCK);
 }
 
-// One fused count launch over `n` device segments.  `err` = the device word
-// the kernel reports skipped windows in (the context's, for ac_check, when NULL).
-// `sc` = the scratch set (one per concurrently running stream); `wave_div` (0, 1
-// = none) limits the launch to 1 / wave_div of its kernel's resident waves, so another
-// launch's waves can be resident beside it.
-// `no_n` (optional, per segment): the segment's image is known to hold no N.
-// `ulen` (optional, per segment): AC_NO_ULEN, or all windows have this length
-// and sit back to back at ceil32(ulen)-base strides (start / length unread).
-// `nrec` (optional, per equal-window segment): its windows carry inline N records (nrec.h).
-// Staged launch (the early-launch stage): the kernel copies each
-// segment's region from src (the pinned block) to dst once the host flags it in
-// host_hdr, and reports its completion there.
-// `hits` (optional): per segment the device matrix the launch also writes its windows' hit words to
-// (DESIGN.md §4e "Hit levels"); refused -- hits_refusal -- unless the launch is bit-sliced.  A staged launch
-// takes the staged hits kernels (the jobs stage, DESIGN.md §4e "Hits from the jobs stage").
-// `pos` (optional, with `hits`): per segment the device matrix of end-position planes the launch writes as
-// well (DESIGN.md §4e "Match end positions"), by the hits-and-positions kernels.
-// `mat_windows` (optional, with `hits`): per segment the window count of the matrix hits[i] / pos[i] point
-// into, when the segment is a window sub-range [lo, hi) of it (the caller has folded row lo into the
-// pointers); NULL: every segment fills its whole matrix.
-ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hipStream_t stream, bool zero,
-                 uint32_t* err, int scratch, uint32_t wave_div, const bool* no_n, const uint32_t* ulen,
-                 const StageLaunch* stage, const bool* nrec, uint32_t* const* hits, uint32_t* const* pos,
-                 const uint32_t* mat_windows) {
+// One fused count launch (ctx.h CountLaunch: what each input means).
+ac_status launch(ac_ctx* ctx, const CountLaunch& rq) {
+    const uint32_t k = rq.k, n = rq.n;
+    const ac_segment* const segs = rq.segs;
     ensure_warm(ctx);
-    ac_ctx::Scratch& sc = ctx->sc[scratch];
+    ac_ctx::Scratch& sc = ctx->sc[rq.scratch];
     if (ac_status st = check_k(ctx, k)) return st;
     if (n > AC_MAX_SEGS) return fail(ctx, AC_ERR_INVALID, "too many segments in one launch (max 4)");
     if (n && !segs) return fail(ctx, AC_ERR_INVALID, "segments is NULL");
     const uint32_t P = acamd::pack_factor(k);
-    const bool staged = stage != nullptr;
+    const bool staged = rq.stage != nullptr;
     acamd::LaunchArgs a;
     std::memset(&a, 0, sizeof a);
     a.n_segs = n;
@@ -107,40 +83,41 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
     // groups; its work items are rows of windows.
     bool live[AC_MAX_SEGS];
     for (uint32_t i = 0; i < n; ++i) live[i] = segs[i].n_kmers && segs[i].sample.n_windows;
-    const bool bs = acamd::bs_launch(k, n, live, ulen);
+    const bool bs = acamd::bs_launch(k, n, live, rq.ulen);
     // The context's edit budget (ac_set_max_errors): another one than 2 counts on a bit-sliced launch
     // or not at all -- refused here, before anything is enqueued.
     const uint32_t E = ctx->max_errors;
     // (hits first: its refusal names the hits call's own constraint)
-    if (hits) {
+    if (rq.hits) {
         bool has_pos[AC_MAX_SEGS];
-        for (uint32_t i = 0; i < n; ++i) has_pos[i] = pos && pos[i];
-        if (const char* why = pos ? acamd::positions_refusal(E, k, n, live, ulen, !ctx->peers.empty(), has_pos)
-                                  : acamd::hits_refusal(E, k, n, live, ulen, !ctx->peers.empty()))
+        for (uint32_t i = 0; i < n; ++i) has_pos[i] = rq.pos && rq.pos[i];
+        if (const char* why = rq.pos ? acamd::positions_refusal(E, k, n, live, rq.ulen, !ctx->peers.empty(), has_pos)
+                                     : acamd::hits_refusal(E, k, n, live, rq.ulen, !ctx->peers.empty()))
             return fail(ctx, AC_ERR_INVALID, why);
         for (uint32_t i = 0; i < n; ++i)
-            if (mat_windows && live[i] && mat_windows[i] < segs[i].sample.n_windows)
+            if (rq.mat_windows && live[i] && rq.mat_windows[i] < segs[i].sample.n_windows)
                 return fail(ctx, AC_ERR_INVALID, "window hits: a segment has more windows than its matrix");
         for (uint32_t i = 0; i < n; ++i)
-            if (live[i] && !hits[i]) return fail(ctx, AC_ERR_INVALID, "window hits: hits[i] is NULL for a segment with work");
+            if (live[i] && !rq.hits[i])
+                return fail(ctx, AC_ERR_INVALID, "window hits: hits[i] is NULL for a segment with work");
         for (uint32_t i = 0; i < n; ++i)
             for (uint32_t j = i + 1; j < n; ++j)
                 if (live[i] && live[j] && segs[i].counts < segs[j].counts + segs[j].n_kmers &&
                     segs[j].counts < segs[i].counts + segs[i].n_kmers)
                     return fail(ctx, AC_ERR_INVALID, "window hits: segments' count vectors overlap");
     }
-    if (pos && !hits) return fail(ctx, AC_ERR_INVALID, "window positions come with the window hits");
-    if (const char* why = acamd::budget_refusal(E, k, n, live, ulen)) return fail(ctx, AC_ERR_INVALID, why);
+    if (rq.pos && !rq.hits) return fail(ctx, AC_ERR_INVALID, "window positions come with the window hits");
+    if (const char* why = acamd::budget_refusal(E, k, n, live, rq.ulen)) return fail(ctx, AC_ERR_INVALID, why);
     const uint32_t cpw = acamd::launch_group_size(k, staged, bs);
     uint64_t items = 0;
     for (uint32_t i = 0; i < n; ++i) {
         const ac_segment& s = segs[i];
         if (s.n_kmers && (!s.kmers || !s.counts)) return fail(ctx, AC_ERR_INVALID, "segment kmers/counts is NULL");
-        const bool equal = ulen && ulen[i] != AC_NO_ULEN;  // windows back to back at ceil32(ulen[i])
+        const bool equal = rq.ulen && rq.ulen[i] != AC_NO_ULEN;  // windows back to back at ceil32(ulen[i])
         if (s.n_kmers && s.sample.n_windows &&
             (!s.sample.codes || !s.sample.nmask || (!equal && (!s.sample.start || !s.sample.length))))
             return fail(ctx, AC_ERR_INVALID, "segment sample has a NULL array");
-        if (equal && (uint64_t)s.sample.n_windows * ((ulen[i] + 31ull) & ~31ull) > s.sample.n_bases)
+        if (equal && (uint64_t)s.sample.n_windows * ((rq.ulen[i] + 31ull) & ~31ull) > s.sample.n_bases)
             return fail(ctx, AC_ERR_INVALID, "equal windows reach past n_bases");
         if (s.sample.n_bases % 32 || s.sample.n_bases >= AC_MAX_IMAGE_BASES)
             return fail(ctx, AC_ERR_INVALID, "sample n_bases must be a multiple of 32 below 2^34");
@@ -165,18 +142,15 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
     // to its windows, so every sub-queue holds about the same work.  Workgroups
     // of AC_WAVES_PER_BLOCK waves are dealt round-robin over blocks of that many
     // consecutive sub-queues (one candidate group each).
-    uint32_t& res_p = !bs    ? ctx->resident[staged][P]
-                      : pos  ? (staged ? ctx->resident_bsps : ctx->resident_bsp)[E == 3u][k]
-                      : hits ? (staged ? ctx->resident_bshs : ctx->resident_bsh)[E == 3u][k]
-                             : E == 3u ? ctx->resident_bs3[staged][k] : ctx->resident_bs[staged][k];
+    const acamd::BsFamily family = acamd::bs_family(staged, rq.hits != nullptr, rq.pos != nullptr, E);
+    uint32_t& res_p = bs ? ctx->resident_bs[acamd::bs_family_index(family)][k] : ctx->resident[staged][P];
     if (!res_p)
-        AC_HIP(ctx, bs ? acamd::resident_waves_bs(k, staged, ctx->cu_count, &res_p, E == 3u ? 3u : 2u, hits != nullptr,
-                                                     pos != nullptr)
+        AC_HIP(ctx, bs ? acamd::resident_waves_bs(family, k, ctx->cu_count, &res_p)
                        : acamd::resident_waves(P, staged, ctx->cu_count, &res_p));
-    const uint64_t fit = wave_div > 1 ? std::max<uint64_t>(AC_WAVES_PER_BLOCK, res_p / wave_div / AC_WAVES_PER_BLOCK *
-                                                                                   AC_WAVES_PER_BLOCK)
-                                      : res_p;
-    const uint64_t resident = bs ? bs_launch_waves(k, E, hits != nullptr, pos != nullptr, staged, items, fit) : fit;
+    const uint64_t fit =
+        rq.wave_div > 1 ? std::max<uint64_t>(AC_WAVES_PER_BLOCK, res_p / rq.wave_div / AC_WAVES_PER_BLOCK * AC_WAVES_PER_BLOCK)
+                        : res_p;
+    const uint64_t resident = bs ? bs_launch_waves(family, k, items, fit) : fit;
     const uint32_t wpw = (uint32_t)std::max<uint64_t>(1, (items + resident - 1) / resident);
 #ifdef AC_FORCE_CHUNK  // A/B builds (tools/variants.sh): fixed item size
     const uint32_t chunk = AC_FORCE_CHUNK;
@@ -203,21 +177,21 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
         d.kmers = s.kmers;
         d.codes = s.sample.codes;
         d.nmask = s.sample.nmask;
-        d.has_n = (no_n && no_n[i]) ? 0u : 1u;
-        d.ulen = ulen ? ulen[i] : AC_NO_ULEN;
-        d.nrec = (nrec && nrec[i] && d.ulen != AC_NO_ULEN) ? acamd::nrec_bits(d.ulen) : 0u;
+        d.has_n = (rq.no_n && rq.no_n[i]) ? 0u : 1u;
+        d.ulen = rq.ulen ? rq.ulen[i] : AC_NO_ULEN;
+        d.nrec = (rq.nrec && rq.nrec[i] && d.ulen != AC_NO_ULEN) ? acamd::nrec_bits(d.ulen) : 0u;
         d.start = s.sample.start;
         d.length = s.sample.length;
         d.n_bases = s.sample.n_bases;
         d.counts = s.counts;
-        if (stage) {
-            d.stage_src = stage->src[i];
-            d.stage_dst = stage->dst[i];
-            d.stage_chunks = stage->chunks[i];
-            d.stage_codes_off = stage->codes_off[i];
-            d.dp_src = stage->dp_src[i];
-            d.dp_off = stage->dp_off[i];
-            d.dp_src_bytes = stage->dp_bytes[i];
+        if (rq.stage) {
+            d.stage_src = rq.stage->src[i];
+            d.stage_dst = rq.stage->dst[i];
+            d.stage_chunks = rq.stage->chunks[i];
+            d.stage_codes_off = rq.stage->codes_off[i];
+            d.dp_src = rq.stage->dp_src[i];
+            d.dp_off = rq.stage->dp_off[i];
+            d.dp_src_bytes = rq.stage->dp_bytes[i];
         }
         d.n_kmers = s.n_kmers;
         d.n_windows = s.sample.n_windows;
@@ -237,7 +211,7 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
         } else {
             d.queue_begin = ~0u;  // never selected by the kernel's segment lookup
             // no workgroup writes this segment's counts
-            if (zero && s.n_kmers) AC_HIP(ctx, hipMemsetAsync(s.counts, 0, sizeof(uint32_t) * s.n_kmers, stream));
+            if (rq.zero && s.n_kmers) AC_HIP(ctx, hipMemsetAsync(s.counts, 0, sizeof(uint32_t) * s.n_kmers, rq.stream));
         }
     }
     // The group's last workgroup stores its counts (no memset), unless live
@@ -250,25 +224,25 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
             if (x.queue_begin == ~0u || y.queue_begin == ~0u) continue;
             alias = x.counts < y.counts + y.n_kmers && y.counts < x.counts + x.n_kmers;
         }
-    a.add_counts = (!zero || alias) ? 1u : 0u;
-    if (zero && alias)
+    a.add_counts = (!rq.zero || alias) ? 1u : 0u;
+    if (rq.zero && alias)
         for (uint32_t i = 0; i < n; ++i)
             if (a.seg[i].queue_begin != ~0u)
-                AC_HIP(ctx, hipMemsetAsync(a.seg[i].counts, 0, sizeof(uint32_t) * a.seg[i].n_kmers, stream));
+                AC_HIP(ctx, hipMemsetAsync(a.seg[i].counts, 0, sizeof(uint32_t) * a.seg[i].n_kmers, rq.stream));
     if (acc_slots > sc.acc_cap) {
         if (sc.acc) AC_HIP(ctx, hipFree(sc.acc));
         sc.acc = nullptr;
         sc.acc_cap = 0;
         AC_HIP(ctx, hipMalloc(&sc.acc, sizeof(uint64_t) * acc_slots));
-        AC_HIP(ctx, hipMemsetAsync(sc.acc, 0, sizeof(uint64_t) * acc_slots, stream));
+        AC_HIP(ctx, hipMemsetAsync(sc.acc, 0, sizeof(uint64_t) * acc_slots, rq.stream));
         sc.acc_cap = acc_slots;
     }
     a.acc = sc.acc;
-    a.err = err ? err : ctx->d_err;
+    a.err = rq.err ? rq.err : ctx->d_err;
     const uint32_t n_counters = qbegin;
     if (n_counters) wave = std::max<uint64_t>(resident, n_counters);
     // a staged launch's device words follow its sub-queue counters in the bank (zeroed with them)
-    const uint32_t used = n_counters + (stage ? AC_STAGE_LINES : 0u);
+    const uint32_t used = n_counters + (rq.stage ? AC_STAGE_LINES : 0u);
     if (used > sc.qcap) {
         if (sc.queue) AC_HIP(ctx, hipFree(sc.queue));
         sc.queue = nullptr;
@@ -276,7 +250,7 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
         const uint32_t cap = std::max<uint32_t>(used, 1024);
         const size_t bytes = sizeof(uint32_t) * AC_QUEUE_LINE * 2 * (size_t)cap;
         AC_HIP(ctx, hipMalloc(&sc.queue, bytes));
-        AC_HIP(ctx, hipMemsetAsync(sc.queue, 0, bytes, stream));
+        AC_HIP(ctx, hipMemsetAsync(sc.queue, 0, bytes, rq.stream));
         sc.qcap = cap;
         sc.bank = 0;
         sc.dirty[0] = sc.dirty[1] = 0;
@@ -286,9 +260,9 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
     a.bank = sc.bank;
     a.zero_count = sc.dirty[sc.bank ^ 1u];
     a.n_queues = std::max<uint32_t>(1, n_counters);
-    if (stage) {
+    if (rq.stage) {
         uint32_t total_chunks = 0;
-        for (uint32_t i = 0; i < n; ++i) total_chunks += stage->chunks[i];
+        for (uint32_t i = 0; i < n; ++i) total_chunks += rq.stage->chunks[i];
         if (total_chunks > sc.stage_gen_cap) {  // (zeroed once: generations are never 0)
             if (sc.stage_gen) AC_HIP(ctx, hipFree(sc.stage_gen));
             sc.stage_gen = nullptr;
@@ -296,24 +270,24 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
             const uint32_t cap = std::max<uint32_t>(total_chunks, 1024);
             const size_t bytes = sizeof(uint32_t) * AC_QUEUE_LINE * (size_t)cap;  // one line per chunk flag
             AC_HIP(ctx, hipMalloc(&sc.stage_gen, bytes));
-            AC_HIP(ctx, hipMemsetAsync(sc.stage_gen, 0, bytes, stream));
+            AC_HIP(ctx, hipMemsetAsync(sc.stage_gen, 0, bytes, rq.stream));
             sc.stage_gen_cap = cap;
         }
         uint32_t off = 0;
         for (uint32_t i = 0; i < n; ++i) {
             a.seg[i].stage_gen = sc.stage_gen + (size_t)off * AC_QUEUE_LINE;
-            off += stage->chunks[i];
+            off += rq.stage->chunks[i];
         }
         a.staged = 1;
-        a.gen = stage->gen;
-        a.host_hdr = stage->host_hdr;
+        a.gen = rq.stage->gen;
+        a.host_hdr = rq.stage->host_hdr;
         a.stage = sc.queue + ((uint64_t)sc.bank * sc.qcap + n_counters) * AC_QUEUE_LINE;
         a.err = a.stage + AC_STAGE_L_ERR * AC_QUEUE_LINE;
-        a.err_out = stage->err_out;
-        a.tag = stage->tag;
-        a.grp_err = stage->grp_err;
+        a.err_out = rq.stage->err_out;
+        a.tag = rq.stage->tag;
+        a.grp_err = rq.stage->grp_err;
         const uint64_t blocks = (wave + AC_WAVES_PER_BLOCK - 1) / AC_WAVES_PER_BLOCK;
-        a.copier_wgs = (uint32_t)std::min<uint64_t>(blocks, stage->copiers);
+        a.copier_wgs = (uint32_t)std::min<uint64_t>(blocks, rq.stage->copiers);
     }
     // the equal-window instantiation when every live segment has equal windows (their fit in the
     // image checked above)
@@ -324,21 +298,21 @@ ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hi
     // last live segment whose queue_begin <= its sub-queue.
     a.bs = bs ? 1u : 0u;
     a.max_errors = E;
-    if (hits) {
+    if (rq.hits) {
         a.want_hits = 1u;
-        for (uint32_t i = 0; i < n; ++i) a.hits[i] = a.seg[i].queue_begin != ~0u ? hits[i] : nullptr;
-        for (uint32_t i = 0; i < n; ++i) a.mat_nw[i] = mat_windows ? mat_windows[i] : a.seg[i].n_windows;
+        for (uint32_t i = 0; i < n; ++i) a.hits[i] = a.seg[i].queue_begin != ~0u ? rq.hits[i] : nullptr;
+        for (uint32_t i = 0; i < n; ++i) a.mat_nw[i] = rq.mat_windows ? rq.mat_windows[i] : a.seg[i].n_windows;
     }
-    if (pos) {
+    if (rq.pos) {
         a.want_pos = 1u;
-        for (uint32_t i = 0; i < n; ++i) a.pos[i] = a.seg[i].queue_begin != ~0u ? pos[i] : nullptr;
+        for (uint32_t i = 0; i < n; ++i) a.pos[i] = a.seg[i].queue_begin != ~0u ? rq.pos[i] : nullptr;
     }
     a.total_waves = wave;
     if (wave) ctx->last_kernel = bs ? 1 : 0;
     ctx->last_waves = wave;
     ctx->last_wpw = wpw;
     ctx->last_groups = groups_total;
-    AC_HIP(ctx, acamd::launch_wm2_count(a, stream));
+    AC_HIP(ctx, acamd::launch_wm2_count(a, rq.stream));
     if (wave) {  // the launch dequeued from `bank` and zeroed the other one
         sc.dirty[sc.bank] = used;
         sc.dirty[sc.bank ^ 1u] = 0;

@@ -1,5 +1,5 @@
 // ctx.h -- the context and the helpers shared by the C-ABI translation units (capi.cpp,
-// count_launch.cpp, capi_exact.cpp, capi_comm.cpp, jobs_stage.cpp).  Private to the library:
+// count_launch.cpp, capi_exact.cpp, capi_comm.cpp, capi_cooc.cpp, capi_cross.cpp, jobs_stage.cpp).  Private to the library:
 // nothing declared here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -24,9 +24,10 @@ struct ac_ctx {
     int cu_count = 256;
     hipStream_t stream = nullptr;
     std::string err;
-    // grow-only device buffers for the host-buffer entry point
-    void* d_buf[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t d_cap[6] = {0, 0, 0, 0, 0, 0};
+    // grow-only device buffers of the samples entry points: every job's k-mers, and their uint32 counts
+    void* d_kmers = nullptr;
+    void* d_counts = nullptr;
+    size_t d_kmers_cap = 0, d_counts_cap = 0;
     std::vector<uint32_t> h_counts;
     // ac_window_hits_samples / ac_window_hits_jobs: the jobs' device hit matrices, one block (grow-only)
     void* d_hits = nullptr;
@@ -91,14 +92,9 @@ struct ac_ctx {
     hipEvent_t sub_zero_ev = nullptr;
     // resident waves of the count kernel per pattern pack P (0 = not queried yet)
     uint32_t resident[2][AC_MAX_PACK + 1] = {};  // [staged][P]
-    uint32_t resident_bs[2][33] = {};            // [staged][k]: the bit-sliced kernel for k (16: queried by the
-                                                 // warm-up; another k at its first launch)
-    uint32_t resident_bs3[2][33] = {};           // the same for the E = 3 kernels (bs3_count.hip), each queried
-                                                 // at its first launch
-    uint32_t resident_bsh[2][33] = {};           // the hits-writing kernels (bsh_count.hip): [E == 3][k]
-    uint32_t resident_bsp[2][33] = {};           // the hits-and-positions kernels (bsp_count.hip), likewise
-    uint32_t resident_bshs[2][33] = {};          // their staged forms (bshs_count.hip, bsps_count.hip), likewise
-    uint32_t resident_bsps[2][33] = {};
+    // ... and of the bit-sliced kernels: [bs_family_index(family)][k] (wm_count.h).  The warm-up queries
+    // the counting kernels for k = 16, plain and staged; every other one is queried at its first launch.
+    uint32_t resident_bs[acamd::BS_FAMILIES][33] = {};
     // The edit budget E of the approximate counts (ac_set_max_errors; M1(E): a window adds
     // max(0, E + 1 - d)): 2 = the reference's.  Another one counts on bit-sliced launches only
     // (stage_plan.h budget_refusal); on an ac_create_multi context every shard holds the same value.
@@ -142,7 +138,7 @@ struct ac_ctx {
     // parsing and exact count instead.
     std::thread warm;
     uint32_t warm_resident[2][AC_MAX_PACK + 1] = {};
-    uint32_t warm_resident_bs[2][33] = {};
+    uint32_t warm_resident_bs[acamd::BS_FAMILIES][33] = {};
 };
 
 namespace ac_detail {
@@ -197,11 +193,42 @@ struct StageLaunch {
 uint32_t stage_copiers(uint64_t tickets);
 // Joins ac_create's warm-up thread (once) and takes the resident-wave counts it queried.
 void ensure_warm(ac_ctx* ctx);
-ac_status launch(ac_ctx* ctx, uint32_t k, const ac_segment* segs, uint32_t n, hipStream_t stream,
-                 bool zero, uint32_t* err = nullptr, int scratch = 0, uint32_t wave_div = 0,
-                 const bool* no_n = nullptr, const uint32_t* ulen = nullptr, const StageLaunch* stage = nullptr,
-                 const bool* nrec = nullptr, uint32_t* const* hits = nullptr,
-                 uint32_t* const* pos = nullptr, const uint32_t* mat_windows = nullptr);
+// One fused count launch over `n` device segments `segs` of k-mer length k, enqueued on `stream`.
+struct CountLaunch {
+    CountLaunch(uint32_t k_, const ac_segment* segs_, uint32_t n_, hipStream_t stream_)
+        : k(k_), segs(segs_), n(n_), stream(stream_) {}
+    uint32_t k;
+    const ac_segment* segs;
+    uint32_t n;
+    hipStream_t stream;
+    // what a call may set beside them:
+    bool zero = true;         // the counts are stored; false: added to what the segments' count vectors hold
+    uint32_t* err = nullptr;  // the device word the kernel reports skipped windows in (NULL: the context's, for ac_check)
+    int scratch = 0;          // the scratch set (ac_ctx::sc: one per concurrently running stream)
+    // (0, 1 = none) limits the launch to 1 / wave_div of its kernel's resident waves, so another launch's
+    // waves can be resident beside it
+    uint32_t wave_div = 0;
+    const bool* no_n = nullptr;  // (optional, per segment) the segment's image is known to hold no N
+    // (optional, per segment) AC_NO_ULEN, or all windows have this length and sit back to back at
+    // ceil32(ulen)-base strides (start / length unread)
+    const uint32_t* ulen = nullptr;
+    // A staged launch (the early-launch stage): the kernel copies each segment's region from
+    // src (the pinned block) to dst once the host flags it in host_hdr, and reports its completion there.
+    const StageLaunch* stage = nullptr;
+    const bool* nrec = nullptr;  // (optional, per equal-window segment) its windows carry inline N records (nrec.h)
+    // (optional) per segment the device matrix the launch also writes its windows' hit words to (DESIGN.md §4e
+    // "Hit levels"); refused -- hits_refusal -- unless the launch is bit-sliced.  A staged launch takes the
+    // staged hits kernels (the jobs stage, DESIGN.md §4e "Hits from the jobs stage").
+    uint32_t* const* hits = nullptr;
+    // (optional, with `hits`) per segment the device matrix of end-position planes the launch writes as well
+    // (DESIGN.md §4e "Match end positions"), by the hits-and-positions kernels
+    uint32_t* const* pos = nullptr;
+    // (optional, with `hits`) per segment the window count of the matrix hits[i] / pos[i] point into, when the
+    // segment is a window sub-range [lo, hi) of it (the caller has folded row lo into the pointers); NULL:
+    // every segment fills its whole matrix
+    const uint32_t* mat_windows = nullptr;
+};
+ac_status launch(ac_ctx* ctx, const CountLaunch& rq);
 
 // --- capi_comm.cpp
 void comm_destroy(ac_ctx* ctx);  // the context's communicator, if it has one (ac_destroy)

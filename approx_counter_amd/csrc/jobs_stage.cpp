@@ -272,6 +272,20 @@ struct PartMats {
     }
 };
 
+// What the stage's two launches (the early one and the DMA path's) ask of launch() alike.
+CountLaunch count_request(const StageCall& c, const ac_segment* segs, const PartMats& mats, const bool* no_n) {
+    CountLaunch rq(c.k, segs, c.p.n, c.stream);
+    rq.zero = c.zero;
+    rq.scratch = c.p.scratch;
+    rq.no_n = no_n;
+    rq.ulen = c.p.ulen;
+    rq.nrec = c.p.nrec;
+    rq.hits = c.hits ? mats.hits : nullptr;
+    rq.pos = c.hits && c.pos ? mats.pos : nullptr;
+    rq.mat_windows = c.p.mat_windows;
+    return rq;
+}
+
 // Device packing: device-visible addresses of the device-packed jobs' Dna5 bytes and
 // window offsets, and the bytes readable from the former.
 struct DevicePack {
@@ -470,9 +484,9 @@ struct EarlyRun {
         ac_segment segs[AC_MAX_JOBS];
         make_segs(c.jobs, p, m, c.d_counts, segs);
         const PartMats mats(c);
-        if (ac_status st = launch(c.ctx, c.k, segs, p.n, c.stream, c.zero, nullptr, p.scratch, 0, no_n, p.ulen, &stg, p.nrec,
-                                  c.hits ? mats.hits : nullptr, c.hits && c.pos ? mats.pos : nullptr, p.mat_windows))
-            return st;
+        CountLaunch rq = count_request(c, segs, mats, no_n);
+        rq.stage = &stg;
+        if (ac_status st = launch(c.ctx, rq)) return st;
         clk.mark(PH_LAUNCH_ENQ);
         launched = true;
         return AC_OK;
@@ -709,10 +723,10 @@ ac_status run_dma(const StageCall& c, const std::vector<Task>& tasks, const Slot
     // the synchronous path reads the error word back with the counts; a
     // submit reports through the context's word (ac_check)
     const PartMats mats(c);
-    if (ac_status st = launch(ctx, c.k, segs, p.n, c.stream, c.zero, c.d_counts ? nullptr : (uint32_t*)(m.hd + p.off_err),
-                              p.scratch, c.wave_div, no_n, p.ulen, nullptr, p.nrec, c.hits ? mats.hits : nullptr,
-                              c.hits && c.pos ? mats.pos : nullptr, p.mat_windows))
-        return st;
+    CountLaunch rq = count_request(c, segs, mats, no_n);
+    rq.err = c.d_counts ? nullptr : (uint32_t*)(m.hd + p.off_err);
+    rq.wave_div = c.wave_div;
+    if (ac_status st = launch(ctx, rq)) return st;
     clk.mark(PH_LAUNCH_ENQ);
     clk.mark(PH_D2H_ENQ);
     AC_HIP(ctx, hipEventRecord(m.sl->ev, c.stream));

@@ -192,35 +192,6 @@ inline uint32_t cands_per_wave(uint32_t P, bool staged) { return 64u * P * (uint
 // groups with launch_group_size (stage_plan.h).
 constexpr uint32_t BS_GROUP = 64u * 2u * (uint32_t)words_for(2, false);
 static_assert(words_for(2, false) == words_for(2, true), "one group size for plain and staged launches");
-#ifndef BS_WAVES_PER_SIMD
-#define BS_WAVES_PER_SIMD 4  // resident waves per SIMD of the bit-sliced kernel for k = 16
-#endif
-#ifndef BS_WAVES_PER_SIMD_MID
-#define BS_WAVES_PER_SIMD_MID 3  // ... for k = 18..BS_K_MID
-#endif
-#ifndef BS_K_MID
-#define BS_K_MID 23  // (k = 24: the staged kernel spills VGPRs inside the NFA block at 3 waves)
-#endif
-// Resident waves per SIMD of the bit-sliced kernel for pattern length k: the NFA state is 3 k
-// registers and a base's table rows 2 k more, so the wider instantiations run at the highest residency
-// whose register budget holds them without scratch access inside the 4-base block (DESIGN.md §4e).
-// Both __launch_bounds__ and the LDS allocation that caps residency take it from here.
-// An edit budget of 3 (bs3_count.hip) is a fourth row, 4 k registers of state: 3 waves up to BS3_K_MID, then 2;
-// from BS3_ONE_BASE_K on the block holds one base's table rows at a time instead of two (bs_block4), which
-// is what keeps k = 29..32 at 2 waves without scratch access inside the block (DESIGN.md 4e "Edit budget").
-#ifndef BS3_K_MID
-#define BS3_K_MID 19
-#endif
-#ifndef BS3_ONE_BASE_K
-#define BS3_ONE_BASE_K 29
-#endif
-constexpr int bs_waves_per_simd(int k, int max_errors = 2) {
-    return max_errors == 3 ? (k <= BS3_K_MID ? 3 : 2)
-                           : k <= 16 ? BS_WAVES_PER_SIMD : k <= BS_K_MID ? BS_WAVES_PER_SIMD_MID : 2;
-}
-// The hits-writing family (bsh_count.hip): the counting twin's residency for every K -- the stores sit
-// outside the 4-base block and the compiler's occupancy equals it (profiles/r12_bsh_codegen.txt).
-constexpr int bsh_waves_per_simd(int k, int max_errors = 2) { return bs_waves_per_simd(k, max_errors); }
 inline __host__ __device__ uint32_t bs_lane_shift(uint32_t n) {
     const uint32_t blocks = (n + 31u) / 32u;
     uint32_t s = 1;
@@ -233,9 +204,62 @@ inline uint64_t bs_rows(uint32_t n_kmers, uint32_t g, uint32_t cpw, uint32_t n_w
     const uint32_t wpr = 64u >> bs_lane_shift(n);
     return ((uint64_t)n_windows + wpr - 1u) / wpr;
 }
+
+// A family of bit-sliced kernels: what a launch asks of the body beyond k.  Everything that differs from
+// one family to the next -- the kernel, its residency, its slot in the context's resident-wave cache -- is
+// looked up by this key.
+enum class BsOut { Count, Hits, Pos };  // what a window leaves: counts; and its hit words; and its end positions
+struct BsFamily {
+    bool staged;  // the early launch's kernel, which stages its own inputs
+    BsOut out;
+    int rows;  // NFA rows: 3 (edit budgets 0..2) or 4 (budget 3)
+};
+// The one place that names a family from a launch's four facts (positions come with hits).
+constexpr BsFamily bs_family(bool staged, bool hits, bool pos, uint32_t max_errors) {
+    return BsFamily{staged, pos ? BsOut::Pos : hits ? BsOut::Hits : BsOut::Count, max_errors == 3u ? 4 : 3};
+}
+constexpr int BS_FAMILIES = 12;
+constexpr int bs_family_index(BsFamily f) { return ((int)f.out * 2 + (f.staged ? 1 : 0)) * 2 + (f.rows == 4 ? 1 : 0); }
+constexpr bool bs_family_indices_distinct() {
+    uint32_t seen = 0;
+    for (int staged = 0; staged < 2; ++staged)
+        for (int hits = 0; hits < 2; ++hits)
+            for (int pos = 0; pos <= hits; ++pos)
+                for (uint32_t e = 2; e <= 3; ++e) {
+                    const int i = bs_family_index(bs_family(staged != 0, hits != 0, pos != 0, e));
+                    if (i < 0 || i >= BS_FAMILIES || (seen >> i & 1u)) return false;
+                    seen |= 1u << i;
+                }
+    return seen == (1u << BS_FAMILIES) - 1u;
+}
+static_assert(bs_family_indices_distinct(), "twelve families, twelve slots");
+
+// Resident waves per SIMD of the bit-sliced kernel of family f for pattern length k: the NFA state is 3 k
+// registers and a base's table rows 2 k more, so the wider instantiations run at the highest residency
+// whose register budget holds them without scratch access inside the 4-base block (DESIGN.md §4e).
+// __launch_bounds__, the LDS allocation that caps residency (bs_blocks_per_cu) and the host's launch
+// sizing all take it from here.  The -D knobs are for A/B builds.
+#ifndef BS_WAVES_PER_SIMD
+#define BS_WAVES_PER_SIMD 4  // counting, three rows: k = 16
+#endif
+#ifndef BS_WAVES_PER_SIMD_MID
+#define BS_WAVES_PER_SIMD_MID 3  // ... k = 18..BS_K_MID, then 2
+#endif
+#ifndef BS_K_MID
+#define BS_K_MID 23  // (k = 24: the staged kernel spills VGPRs inside the NFA block at 3 waves)
+#endif
+// An edit budget of 3 (bs3_count.hip) is a fourth row, 4 k registers of state: 3 waves up to BS3_K_MID, then 2;
+// from BS3_ONE_BASE_K on the block holds one base's table rows at a time instead of two (bs_block4), which
+// is what keeps k = 29..32 at 2 waves without scratch access inside the block (DESIGN.md 4e "Edit budget").
+#ifndef BS3_K_MID
+#define BS3_K_MID 19
+#endif
+#ifndef BS3_ONE_BASE_K
+#define BS3_ONE_BASE_K 29
+#endif
 // The hits-and-positions family (bsp_count.hip): eight position planes and per-base hit accumulation more
-// in registers, so the highest residency with no scratch, buffer or global access inside the 4-base block
-// is re-derived per (K, rows) from the compiler's remarks (profiles/r14_bsp_codegen.txt).
+// in registers, so its residency is re-derived per (K, rows) from the compiler's remarks
+// (profiles/r14_bsp_codegen.txt).
 #ifndef BSP_WAVES_PER_SIMD_16
 #define BSP_WAVES_PER_SIMD_16 4  // three rows, k = 16
 #endif
@@ -251,12 +275,8 @@ inline uint64_t bs_rows(uint32_t n_kmers, uint32_t g, uint32_t cpw, uint32_t n_w
 #ifndef BSP3_ONE_BASE_K
 #define BSP3_ONE_BASE_K 26  // four rows: one base's table rows at a time from here on (BS3_ONE_BASE_K's sibling)
 #endif
-constexpr int bsp_waves_per_simd(int k, int max_errors = 2) {
-    return max_errors == 3 ? (k <= BSP3_K_MID ? 3 : k < BSP3_K_ONE ? 2 : 1)
-                           : k <= 16 ? BSP_WAVES_PER_SIMD_16 : k <= BSP_K_MID ? 3 : 2;
-}
 // The staged hits-writing family (bshs_count.hip: the early launch and device packing of ac_window_hits_jobs)
-// and the staged hits-and-positions family (bsps_count.hip), re-derived per (K, rows) like the families above
+// and the staged hits-and-positions family (bsps_count.hip), re-derived likewise
 // (profiles/r15_bshs_codegen.txt): the staged frame's state costs registers the plain kernels do not hold.
 #ifndef BSHS_WAVES_PER_SIMD_16
 #define BSHS_WAVES_PER_SIMD_16 3  // three rows, k = 16: the staged counting kernel sits at exactly 128 VGPRs
@@ -267,9 +287,6 @@ constexpr int bsp_waves_per_simd(int k, int max_errors = 2) {
 #ifndef BSHS3_K_MID
 #define BSHS3_K_MID 19  // four rows: 3 waves up to here, then 2
 #endif
-constexpr int bshs_waves_per_simd(int k, int max_errors = 2) {
-    return max_errors == 3 ? (k <= BSHS3_K_MID ? 3 : 2) : k <= 16 ? BSHS_WAVES_PER_SIMD_16 : k <= BSHS_K_MID ? 3 : 2;
-}
 #ifndef BSPS_WAVES_PER_SIMD_16
 #define BSPS_WAVES_PER_SIMD_16 3
 #endif
@@ -285,26 +302,38 @@ constexpr int bshs_waves_per_simd(int k, int max_errors = 2) {
 #ifndef BSPS3_K_ONE
 #define BSPS3_K_ONE 31  // ... and from here on 1, like the plain family
 #endif
-constexpr int bsps_waves_per_simd(int k, int max_errors = 2) {
-    return max_errors == 3 ? (k <= BSPS3_K_MID ? 3 : k < BSPS3_K_ONE ? 2 : 1)
-                           : k <= 16 ? BSPS_WAVES_PER_SIMD_16 : (k <= BSPS_K_MID && k != BSPS_K_TWO) ? 3 : 2;
+constexpr int bs_waves_per_simd(BsFamily f, int k) {
+    const bool four = f.rows == 4;
+    if (f.out == BsOut::Pos && f.staged)
+        return four ? (k <= BSPS3_K_MID ? 3 : k < BSPS3_K_ONE ? 2 : 1)
+                    : k <= 16 ? BSPS_WAVES_PER_SIMD_16 : (k <= BSPS_K_MID && k != BSPS_K_TWO) ? 3 : 2;
+    if (f.out == BsOut::Pos)
+        return four ? (k <= BSP3_K_MID ? 3 : k < BSP3_K_ONE ? 2 : 1)
+                    : k <= 16 ? BSP_WAVES_PER_SIMD_16 : k <= BSP_K_MID ? 3 : 2;
+    if (f.out == BsOut::Hits && f.staged)
+        return four ? (k <= BSHS3_K_MID ? 3 : 2) : k <= 16 ? BSHS_WAVES_PER_SIMD_16 : k <= BSHS_K_MID ? 3 : 2;
+    // counting, plain and staged, and the plain hits-writing family (bsh_count.hip): its stores sit outside
+    // the 4-base block and the compiler's occupancy equals its counting twin's (profiles/r12_bsh_codegen.txt)
+    return four ? (k <= BS3_K_MID ? 3 : 2) : k <= 16 ? BS_WAVES_PER_SIMD : k <= BS_K_MID ? BS_WAVES_PER_SIMD_MID : 2;
 }
-hipError_t resident_waves_bs(uint32_t k, bool staged, int cu_count, uint32_t* waves, uint32_t max_errors = 2,
-                             bool hits = false, bool pos = false);
-// bs3_count.hip: the E = 3 kernel for k (AC_BS_K_LIST), plain or staged; nullptr if there is none
-void (*bs3_kernel(uint32_t k, bool staged))(LaunchArgs);
-// bsh_count.hip: the plain hits-writing kernel for k (AC_BS_K_LIST) at edit budget max_errors (0..2: three
-// NFA rows, 3: four); nullptr if there is none
-void (*bsh_kernel(uint32_t k, uint32_t max_errors))(LaunchArgs);
+// Workgroups per CU that a kernel's LDS array leaves room for (each kernel sizes its array as 160 KB over
+// this): its residency -- a kernel at one wave per SIMD takes the LDS of two, its registers cap it.
+constexpr int bs_blocks_per_cu(BsFamily f, int k) {
+    return 4 * (bs_waves_per_simd(f, k) > 2 ? bs_waves_per_simd(f, k) : 2) / AC_WAVES_PER_BLOCK;
+}
+
+typedef void (*CountKernel)(LaunchArgs);
+// The family translation units' pickers: the kernel of family f for k (AC_BS_K_LIST), nullptr if there is
+// none.  Each serves the families its unit holds: bs3_count.hip counting at four rows (plain and staged),
+// bsh_count.hip / bsp_count.hip the plain hits and hits-and-positions kernels, bshs_count.hip /
+// bsps_count.hip their staged forms (three rows and four).
+typedef CountKernel BsPicker(uint32_t k, BsFamily f);
+BsPicker bs3_kernel, bsh_kernel, bsp_kernel, bshs_kernel, bsps_kernel;
+hipError_t resident_waves_bs(BsFamily f, uint32_t k, int cu_count, uint32_t* waves);
 // bsh_count.hip: level_counts[e * n_kmers + c] = the windows of level plane e of a hit matrix that hold
 // candidate c (a column popcount); level_counts is zeroed on the stream first
 hipError_t launch_hit_level_counts(const uint32_t* hits, uint32_t n_kmers, uint32_t n_windows, uint32_t levels,
                                    uint32_t* level_counts, hipStream_t stream);
-// bsp_count.hip: the plain hits-and-positions kernel for k at edit budget max_errors; nullptr if there is none
-void (*bsp_kernel(uint32_t k, uint32_t max_errors))(LaunchArgs);
-// bshs_count.hip / bsps_count.hip: the staged hits-writing and hits-and-positions kernels, likewise
-void (*bshs_kernel(uint32_t k, uint32_t max_errors))(LaunchArgs);
-void (*bsps_kernel(uint32_t k, uint32_t max_errors))(LaunchArgs);
 // bsp_count.hip: profile[(d * n_kmers + c) * window_len + p - 1] = the windows that hold candidate c at
 // distance exactly d with their best occurrence ending at base p (1..window_len), from a hit matrix of
 // `levels` planes and its position matrix; profile is zeroed on the stream first

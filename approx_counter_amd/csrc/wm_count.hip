@@ -636,13 +636,12 @@ __device__ __forceinline__ void count_body(const LaunchArgs& a, BlockLds<words_f
 
 }  // namespace
 
-// The bit-sliced kernel (bs_count.inc): k = K, equal windows.  bs_waves_per_simd(K) waves per SIMD
-// (K = 16: four, <= 128 VGPRs; wider patterns fewer), capped by the LDS allocation like the two-word
-// kernel below.
+// The bit-sliced kernel (bs_count.inc): k = K, equal windows, counting over three rows, at its family's
+// residency (K = 16: four waves per SIMD, <= 128 VGPRs; wider patterns fewer), capped by the LDS allocation
+// like the two-word kernel below.
 template <int K, bool STAGED>
-__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, bs_waves_per_simd(K)) void bs_count_kernel(LaunchArgs a) {
-    constexpr int kBlocksPerCu = 4 * bs_waves_per_simd(K) / WAVES_PER_BLOCK;
-    __shared__ BsLds<K> lds[(160 * 1024 / kBlocksPerCu) / sizeof(BsLds<K>)];
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, bs_waves_per_simd(BsFamily{STAGED, BsOut::Count, 3}, K)) void bs_count_kernel(LaunchArgs a) {
+    __shared__ BsLds<K> lds[(160 * 1024 / bs_blocks_per_cu(BsFamily{STAGED, BsOut::Count, 3}, K)) / sizeof(BsLds<K>)];
     bs_body<K, STAGED>(a, lds[0]);
 }
 
@@ -657,21 +656,23 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, waves_per_simd(words_for(P, S
 }
 
 namespace {
-// The kernel that counts a launch: word-parallel for pattern pack P (bs_k = 0), or bit-sliced for
-// k = bs_k (AC_BS_K_LIST) -- at an edit budget of 3 one of bs3_count.hip's; nullptr if there is none.
-typedef void (*CountKernel)(LaunchArgs);
-CountKernel count_kernel(uint32_t P, uint32_t bs_k, bool staged, bool eq, uint32_t max_errors = 2u, bool hits = false,
-                         bool pos = false) {
-    if (pos) return !bs_k ? nullptr : staged ? bsps_kernel(bs_k, max_errors) : bsp_kernel(bs_k, max_errors);
-    if (hits) return !bs_k ? nullptr : staged ? bshs_kernel(bs_k, max_errors) : bsh_kernel(bs_k, max_errors);
-    if (bs_k && max_errors == 3u) return bs3_kernel(bs_k, staged);
-    if (bs_k) {
-#define AC_BS_PICK(KK) \
-    if (bs_k == KK) return staged ? bs_count_kernel<KK, true> : bs_count_kernel<KK, false>;
-        AC_BS_K_LIST(AC_BS_PICK)
-#undef AC_BS_PICK
-        return nullptr;
+// The kernel that counts a launch; nullptr if there is none.  Bit-sliced, of family f for k (AC_BS_K_LIST):
+// counting over three rows is this unit's, every other family has a unit and a picker of its own.
+CountKernel bs_kernel(uint32_t k, BsFamily f) {
+    switch (f.out) {
+        case BsOut::Pos: return f.staged ? bsps_kernel(k, f) : bsp_kernel(k, f);
+        case BsOut::Hits: return f.staged ? bshs_kernel(k, f) : bsh_kernel(k, f);
+        case BsOut::Count: break;
     }
+    if (f.rows == 4) return bs3_kernel(k, f);
+#define AC_BS_PICK(KK) \
+    if (k == KK) return f.staged ? bs_count_kernel<KK, true> : bs_count_kernel<KK, false>;
+    AC_BS_K_LIST(AC_BS_PICK)
+#undef AC_BS_PICK
+    return nullptr;
+}
+// Word-parallel, for pattern pack P.
+CountKernel wm_kernel(uint32_t P, bool staged, bool eq) {
 #define AC_PICK(PP)                                                                                      \
     case PP:                                                                                             \
         return staged ? (eq ? wm2_count_kernel<PP, true, true> : wm2_count_kernel<PP, true, false>)      \
@@ -717,12 +718,11 @@ hipError_t resident_waves(uint32_t P, bool staged, int cu_count, uint32_t* waves
     // (queried on the equal-window kernel, the one the bench's kernel leg, the CLI and the stage launch:
     // the query loads the kernel's code, and that load then is not paid again at its first launch --
     // the instantiations of one word count have the same LDS allocation, so the same residency)
-    return occupancy(count_kernel(P, 0u, staged, true), cu_count, waves);
+    return occupancy(wm_kernel(P, staged, true), cu_count, waves);
 }
 
-hipError_t resident_waves_bs(uint32_t k, bool staged, int cu_count, uint32_t* waves, uint32_t max_errors, bool hits,
-                             bool pos) {
-    return occupancy(count_kernel(0u, k, staged, true, max_errors, hits, pos), cu_count, waves);
+hipError_t resident_waves_bs(BsFamily f, uint32_t k, int cu_count, uint32_t* waves) {
+    return occupancy(bs_kernel(k, f), cu_count, waves);
 }
 
 hipError_t launch_wm2_count(const LaunchArgs& args, hipStream_t stream) {
@@ -736,8 +736,9 @@ hipError_t launch_wm2_count(const LaunchArgs& args, hipStream_t stream) {
     // (hits: bit-sliced launches only -- there is no other kernel that writes them)
     if (args.want_hits && !args.bs) return hipErrorInvalidValue;
     if (args.want_pos && !args.want_hits) return hipErrorInvalidValue;
-    const CountKernel kernel = count_kernel(args.P, args.bs ? args.m : 0u, args.staged != 0u, args.eq != 0u,
-                                            args.max_errors, args.want_hits != 0u, args.want_pos != 0u);
+    const CountKernel kernel =
+        args.bs ? bs_kernel(args.m, bs_family(args.staged != 0u, args.want_hits != 0u, args.want_pos != 0u, args.max_errors))
+                : wm_kernel(args.P, args.staged != 0u, args.eq != 0u);
     if (!kernel) return hipErrorInvalidValue;
     hipLaunchKernelGGL(kernel, grid, block, 0, stream, args);
     return hipGetLastError();

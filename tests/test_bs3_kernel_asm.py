@@ -2,7 +2,8 @@
 NFA rows of bs_nfa_r.h; DESIGN.md §4e "Edit budget"), from one compile of their translation unit: the
 assembly, and the compiler's kernel-resource-usage remarks.
 
-Residency: bs_waves_per_simd(K, 3) (wm_count.h) is what __launch_bounds__ and the LDS allocation declare
+Residency: bs_waves_per_simd(family, K) of the E = 3 counting family (wm_count.h) is what __launch_bounds__
+and the LDS allocation declare
 and what the host assumes when it sizes a launch; for every listed k, plain and staged, it equals the
 occupancy the compiler reports.
 
@@ -32,7 +33,7 @@ DECLARED_SRC = """
 #include "bs_nfa.h"
 #include "wm_count.h"
 int main() {
-#define AC_SHOW(KK) std::printf("%d %d\\n", KK, acamd::bs_waves_per_simd(KK, 3));
+#define AC_SHOW(KK) std::printf("%d %d\\n", KK, acamd::bs_waves_per_simd(acamd::bs_family(false, false, false, 3), KK));
     AC_BS_K_LIST(AC_SHOW)
     return 0;
 }
@@ -62,7 +63,7 @@ def compiled(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def declared(tmp_path_factory):
-    """{K: bs_waves_per_simd(K, 3)} from a host program that includes the kernel's header."""
+    """{K: bs_waves_per_simd(family, K)} from a host program that includes the kernel's header."""
     d = tmp_path_factory.mktemp("decl")
     src, exe = str(d / "declared.cpp"), str(d / "declared")
     with open(src, "w") as fh:

@@ -2,7 +2,8 @@
 over three NFA rows for the edit budgets 0..2 and over four for budget 3; DESIGN.md §4e "Hit levels"), from
 one compile of their translation unit: the assembly, and the compiler's kernel-resource-usage remarks.
 
-Residency: bsh_waves_per_simd(K, E) (wm_count.h) is what __launch_bounds__ and the LDS allocation declare
+Residency: bs_waves_per_simd(family, K) of the plain hits-writing family (wm_count.h) is what
+__launch_bounds__ and the LDS allocation declare
 and what the host assumes when it sizes a launch; for every listed k and both row counts it equals the
 occupancy the compiler reports.
 
@@ -31,7 +32,8 @@ DECLARED_SRC = """
 #include "bs_nfa.h"
 #include "wm_count.h"
 int main() {
-#define AC_SHOW(KK) std::printf("%d %d %d\\n", KK, acamd::bsh_waves_per_simd(KK, 2), acamd::bsh_waves_per_simd(KK, 3));
+#define AC_WAVES(KK, E) acamd::bs_waves_per_simd(acamd::bs_family(false, true, false, E), KK)
+#define AC_SHOW(KK) std::printf("%d %d %d\\n", KK, AC_WAVES(KK, 2), AC_WAVES(KK, 3));
     AC_BS_K_LIST(AC_SHOW)
     return 0;
 }
@@ -61,7 +63,7 @@ def compiled(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def declared(tmp_path_factory):
-    """{(K, R): bsh_waves_per_simd(K, E)} from a host program that includes the kernel's header."""
+    """{(K, R): bs_waves_per_simd(family, K)} from a host program that includes the kernel's header."""
     d = tmp_path_factory.mktemp("decl")
     src, exe = str(d / "declared.cpp"), str(d / "declared")
     with open(src, "w") as fh:

@@ -3,9 +3,9 @@ bsps_count.hip: bs_count.inc's body with STAGED and HITS, and POS, on; DESIGN.md
 stage"), from one compile of each translation unit: the assembly, and the compiler's kernel-resource-usage
 remarks.
 
-Residency: bshs_waves_per_simd(K, E) / bsps_waves_per_simd(K, E) (wm_count.h) are what __launch_bounds__ and
+Residency: bs_waves_per_simd(family, K) of the two staged families (wm_count.h) is what __launch_bounds__ and
 the LDS allocation declare and what the host assumes when it sizes a launch; for every listed k and both row
-counts they equal the occupancy the compiler reports.
+counts it equals the occupancy the compiler reports.
 
 Op budget, for K = 16, 22 and 32: the block of 4 bases -- one copy of the NFA code -- stays within the budget
 its plain twin is held to (tests/test_bsh_kernel_asm.py: the counting kernels' op bounds;
@@ -25,15 +25,16 @@ CSRC = os.path.join(ROOT, "approx_counter_amd", "csrc")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 BASES = 4  # per block (bs_block4)
 ASM_K = [k for k in (16, 22, 32) if k in LISTED_K]
-FAMILIES = {"bshs": "bshs_waves_per_simd", "bsps": "bsps_waves_per_simd"}
+FAMILIES = ("bshs", "bsps")
 
 DECLARED_SRC = """
 #include <cstdio>
 #include "bs_nfa.h"
 #include "wm_count.h"
 int main() {
-#define AC_SHOW(KK) std::printf("%d %d %d %d %d\\n", KK, acamd::bshs_waves_per_simd(KK, 2), acamd::bshs_waves_per_simd(KK, 3), \\
-                                acamd::bsps_waves_per_simd(KK, 2), acamd::bsps_waves_per_simd(KK, 3));
+#define AC_WAVES(KK, POS, E) acamd::bs_waves_per_simd(acamd::bs_family(true, true, POS, E), KK)
+#define AC_SHOW(KK) std::printf("%d %d %d %d %d\\n", KK, AC_WAVES(KK, false, 2), AC_WAVES(KK, false, 3), \\
+                                AC_WAVES(KK, true, 2), AC_WAVES(KK, true, 3));
     AC_BS_K_LIST(AC_SHOW)
     return 0;
 }

@@ -3,7 +3,8 @@ HITS and POS on, over three NFA rows for the edit budgets 0..2 and over four for
 "Match end positions"), from one compile of its translation unit and one of its twin's, bsh_count.hip: the
 assembly, and the compiler's kernel-resource-usage remarks.
 
-Residency: bsp_waves_per_simd(K, E) (wm_count.h) is what __launch_bounds__ and the LDS allocation declare and
+Residency: bs_waves_per_simd(family, K) of the plain hits-and-positions family (wm_count.h) is what
+__launch_bounds__ and the LDS allocation declare and
 what the host assumes when it sizes a launch; for every listed k and both row counts it equals the occupancy
 the compiler reports.
 
@@ -32,7 +33,8 @@ DECLARED_SRC = """
 #include "bs_nfa.h"
 #include "wm_count.h"
 int main() {
-#define AC_SHOW(KK) std::printf("%d %d %d\\n", KK, acamd::bsp_waves_per_simd(KK, 2), acamd::bsp_waves_per_simd(KK, 3));
+#define AC_WAVES(KK, E) acamd::bs_waves_per_simd(acamd::bs_family(false, true, true, E), KK)
+#define AC_SHOW(KK) std::printf("%d %d %d\\n", KK, AC_WAVES(KK, 2), AC_WAVES(KK, 3));
     AC_BS_K_LIST(AC_SHOW)
     return 0;
 }
@@ -71,7 +73,7 @@ def twin(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def declared(tmp_path_factory):
-    """{(K, R): bsp_waves_per_simd(K, E)} from a host program that includes the kernel's header."""
+    """{(K, R): bs_waves_per_simd(family, K)} from a host program that includes the kernel's header."""
     d = tmp_path_factory.mktemp("decl")
     src, exe = str(d / "declared.cpp"), str(d / "declared")
     with open(src, "w") as fh:
