@@ -9,9 +9,9 @@ from .counter import (ApproxCounter, DeviceSegment, Dna5Sample, Jobs, PackedSamp
                       cross_cooccurrence_words,
                       distances_from_hits,
                       error_count, error_levels, hits_words, pack_windows, pinned_copy, pinned_empty, positions_words,
-                      to_dna5, unpack_hits, unpack_positions)
+                      to_dna5, unpack_hits, unpack_positions, unpack_starts)
 from ._lib import ApproxCounterError
 
 __all__ = ["ApproxCounter", "ApproxCounterError", "DeviceSegment", "Dna5Sample", "Jobs", "PackedSample", "WindowHits",
            "cooccurrence_words", "cross_cooccurrence_words", "distances_from_hits", "error_count", "error_levels", "hits_words", "pack_windows", "pinned_copy",
-           "pinned_empty", "to_dna5", "unpack_hits", "positions_words", "unpack_positions"]
+           "pinned_empty", "to_dna5", "unpack_hits", "positions_words", "unpack_positions", "unpack_starts"]

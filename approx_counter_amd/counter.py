@@ -170,18 +170,64 @@ def unpack_positions(planes, hit_E, n_kmers: int) -> np.ndarray:
     return np.where(hit_E, pos + 1, -1).astype(np.int16)
 
 
+def unpack_starts(planes, hit_E, n_kmers: int) -> np.ndarray:
+    """A start matrix's values (ac_hit_start_positions_device): the layout of a position matrix, plane b
+    holding bit b of the start itself.  Returns int16 (n_windows, n_kmers): the 0-based inclusive start of
+    the shortest occurrence ending at the pair's end position at the best distance, -1 where hit_E is
+    False.  Pure numpy."""
+    return np.where(np.asarray(hit_E, dtype=bool), unpack_positions(planes, hit_E, n_kmers) - 1, -1).astype(np.int16)
+
+
 class WindowHits:
     """One part's counts and hit levels (ac_window_hits_samples): which windows hold each k-mer within
     0..E edits -- the reference's tcount[errors][read] (approx_counter.cpp:553-565) before it is summed.
-    From window_hits(..., positions=True) also the match end positions (ac_window_positions_samples)."""
+    From window_hits(..., positions=True) also the match end positions (ac_window_positions_samples); from
+    window_hits(..., spans=True) the match starts as well (ac_window_spans_samples)."""
 
-    def __init__(self, counts, levels, n_kmers: int, planes=None, window_len: int = 0, counter=None):
+    def __init__(self, counts, levels, n_kmers: int, planes=None, window_len: int = 0, counter=None, starts=None,
+                 k: int = 0):
         self.counts = counts
         self.levels = np.asarray(levels, dtype=np.uint32)  # (E + 1, n_windows, words)
         self.n_kmers = int(n_kmers)
         self.planes = None if planes is None else np.asarray(planes, dtype=np.uint32)  # (8, n_windows, words)
+        self.starts = None if starts is None else np.asarray(starts, dtype=np.uint32)  # (8, n_windows, words)
         self.window_len = int(window_len)
+        self.k = int(k)
         self._counter = counter
+
+    def start_positions(self) -> np.ndarray:
+        """int16 (n_windows, n_kmers): where the best occurrence starts (0-based, inclusive: the shortest
+        substring ending at end_positions() at the best distance), -1 where the window does not hold the
+        k-mer within E edits."""
+        if self.starts is None:
+            raise ValueError("no spans: ask window_hits(..., spans=True)")
+        return unpack_starts(self.starts, self.hit(self.max_errors), self.n_kmers)
+
+    def span_lengths(self) -> np.ndarray:
+        """int16 (n_windows, n_kmers): end - start, k - d .. k + d, -1 where there is no hit."""
+        start = self.start_positions()
+        return np.where(start >= 0, self.end_positions() - start, -1).astype(np.int16)
+
+    def length_profile(self) -> np.ndarray:
+        """uint32 (E + 1, n_kmers, 2 E + 1): the windows at distance exactly d whose occurrence has length
+        k - E .. k + E (an insertion lengthens it, a deletion shortens it).  numpy."""
+        if not self.k:
+            raise ValueError("no k-mer length: this object was not made by window_hits(..., spans=True)")
+        E, ln = self.max_errors, self.span_lengths()
+        d = self.distances()
+        prof = np.zeros((E + 1, self.n_kmers, 2 * E + 1), np.uint32)
+        ws, cs = np.nonzero(ln >= 0)
+        at = ln[ws, cs].astype(np.int64) - (self.k - E)
+        ok = (at >= 0) & (at <= 2 * E)
+        np.add.at(prof, (d[ws, cs][ok], cs[ok], at[ok]), 1)
+        return prof
+
+    def start_profile(self) -> np.ndarray:
+        """uint32 (E + 1, n_kmers, L): the windows at distance exactly d whose best occurrence starts at base
+        p, computed on the device (ac_hit_position_profile_device on the start matrix)."""
+        if self.starts is None or self._counter is None:
+            raise ValueError("no spans: ask window_hits(..., spans=True)")
+        return self._profile(self.starts)
 
     def end_positions(self) -> np.ndarray:
         """int16 (n_windows, n_kmers): where the leftmost occurrence at the best distance ends (exclusive,
@@ -193,16 +239,19 @@ class WindowHits:
     def position_profile(self) -> np.ndarray:
         """uint32 (E + 1, n_kmers, L): the windows at distance exactly d whose best occurrence ends at base
         p + 1, computed on the device (ac_hit_position_profile_device)."""
-        import torch
-
         if self.planes is None or self._counter is None:
             raise ValueError("no positions: ask window_hits(..., positions=True)")
+        return self._profile(self.planes)
+
+    def _profile(self, planes) -> np.ndarray:
+        import torch
+
         lv, nw, _ = self.levels.shape
         if not (self.n_kmers and nw):
             return np.zeros((lv, self.n_kmers, self.window_len), np.uint32)
         dev = torch.device("cuda")
         h = torch.from_numpy(self.levels.view(np.int32)).to(dev)
-        p = torch.from_numpy(self.planes.view(np.int32)).to(dev)
+        p = torch.from_numpy(np.ascontiguousarray(planes).view(np.int32)).to(dev)
         out = self._counter.hit_position_profile(h, p, self.n_kmers, nw, lv, self.window_len)
         torch.cuda.synchronize(dev)
         return out.cpu().numpy().view(np.uint32)
@@ -522,7 +571,9 @@ class ApproxCounter:
         w.  Only where the bit-sliced kernel counts (k = 16 or 18..32, every job with work holding equal
         windows of 1..256 bases, a single-device context), at the context's edit budget; anything else raises
         (AC_ERR_INVALID).  positions: ac_window_positions_jobs -- every WindowHits also holds the match end
-        positions (.end_positions(), .position_profile())."""
+        positions (.end_positions(), .position_profile()).  There is no `spans` here: match spans are not built
+        for the jobs stage, whose image keeps N in inline records the span pass does not decode -- use
+        window_hits(..., spans=True)."""
         if not hasattr(self._L, "ac_window_hits_jobs"):
             raise _lib.ApproxCounterError(_lib.AC_ERR_INVALID, "this build of the library has no ac_window_hits_jobs")
         if not isinstance(jobs, Jobs):
@@ -575,17 +626,19 @@ class ApproxCounter:
         """ac_error_count_samples: [(kmers, device sample from upload_sample), ...], one fused launch."""
         return self._sample_jobs(self._L.ac_error_count_samples, k, parts)
 
-    def window_hits(self, k: int, parts, positions: bool = False) -> list:
+    def window_hits(self, k: int, parts, positions: bool = False, spans: bool = False) -> list:
         """ac_window_hits_samples: [(kmers, PackedSample), ...] (up to 4 parts, e.g. both read ends) are
         uploaded into the context's sample slots and counted in one fused launch that also writes every
         window's hit levels; returns one WindowHits per part.  Only where the bit-sliced kernel counts
         (k = 16 or 18..32, equal windows of 1..256 bases, a single-device context), at the context's
         edit budget; anything else raises (AC_ERR_INVALID).  positions: ac_window_positions_samples -- every
-        WindowHits also holds the match end positions (.end_positions(), .position_profile())."""
+        WindowHits also holds the match end positions (.end_positions(), .position_profile()).  spans (implies
+        positions): ac_window_spans_samples -- and the match starts (.start_positions(), .span_lengths(),
+        .length_profile(), .start_profile())."""
         if not hasattr(self._L, "ac_window_hits_samples"):
             raise _lib.ApproxCounterError(_lib.AC_ERR_INVALID, "this build of the library has no ac_window_hits_samples")
-        if positions:
-            return self._window_positions(k, parts)
+        if positions or spans:
+            return self._window_positions(k, parts, spans)
         E = self.max_errors
         keep, arr, mats = [], [], []
         for slot, (km, smp) in enumerate(parts):
@@ -604,27 +657,54 @@ class ApproxCounter:
                            counter=self)
                 for (km, c, nw), m in zip(keep, mats)]
 
-    def _window_positions(self, k: int, parts) -> list:
-        if not hasattr(self._L, "ac_window_positions_samples"):
-            raise _lib.ApproxCounterError(_lib.AC_ERR_INVALID,
-                                          "this build of the library has no ac_window_positions_samples")
+    def _window_positions(self, k: int, parts, spans: bool = False) -> list:
+        name = "ac_window_spans_samples" if spans else "ac_window_positions_samples"
+        if not hasattr(self._L, name):
+            raise _lib.ApproxCounterError(_lib.AC_ERR_INVALID, f"this build of the library has no {name}")
         E = self.max_errors
-        keep, arr, mats, planes = [], [], [], []
+        keep, arr, mats, planes, starts = [], [], [], [], []
         for slot, (km, smp) in enumerate(parts):
             km = np.ascontiguousarray(np.asarray(km, dtype=np.uint64))
             c = np.zeros(max(km.size, 1), dtype=np.uint64)
             mats.append(np.full(max(hits_words(km.size, smp.n_windows, E), 1), 0xFFFFFFFF, dtype=np.uint32))
             planes.append(np.full(max(positions_words(km.size, smp.n_windows), 1), 0xFFFFFFFF, dtype=np.uint32))
+            starts.append(np.full(max(positions_words(km.size, smp.n_windows), 1), 0xFFFFFFFF, dtype=np.uint32))
             keep.append((km, c, smp.n_windows, int(smp.length[0]) if smp.n_windows else 0))
             arr.append(ACSampleJob(_ptr(km if km.size else np.zeros(1, np.uint64), ctypes.c_uint64), int(km.size),
                                    self.upload_sample(smp, slot), _ptr(c, ctypes.c_uint64)))
         a = (ACSampleJob * len(arr))(*arr)
         hp = (_lib.p32 * len(arr))(*[_ptr(m, ctypes.c_uint32) for m in mats])
         pp = (_lib.p32 * len(arr))(*[_ptr(m, ctypes.c_uint32) for m in planes])
-        check(self._L.ac_window_positions_samples(self._h, int(k), a, len(arr), hp, pp), self._h)
+        if spans:
+            sp = (_lib.p32 * len(arr))(*[_ptr(m, ctypes.c_uint32) for m in starts])
+            check(self._L.ac_window_spans_samples(self._h, int(k), a, len(arr), hp, pp, sp), self._h)
+        else:
+            check(self._L.ac_window_positions_samples(self._h, int(k), a, len(arr), hp, pp), self._h)
+        shape = lambda m, km, nw: m[: positions_words(km.size, nw)].reshape(8, nw, (km.size + 31) // 32)  # noqa: E731
         return [WindowHits(c[: km.size], m[: hits_words(km.size, nw, E)].reshape(E + 1, nw, (km.size + 31) // 32), km.size,
-                           p[: positions_words(km.size, nw)].reshape(8, nw, (km.size + 31) // 32), L, self)
-                for (km, c, nw, L), m, p in zip(keep, mats, planes)]
+                           shape(p, km, nw), L, self, shape(t, km, nw) if spans else None, int(k))
+                for (km, c, nw, L), m, p, t in zip(keep, mats, planes, starts)]
+
+    def hit_start_positions(self, k: int, kmers, n_kmers: int, sample, window_len: int, hits, pos, levels: int,
+                            out=None, stream=None):
+        """ac_hit_start_positions_device: the span pass alone over resident tensors -- `kmers` the device
+        k-mers (int64 / uint64 words), `sample` an ACWindows of device pointers (or a DeviceSegment) holding
+        equal windows of window_len bases, `hits` a device hit matrix of `levels` planes, `pos` its position
+        matrix.  Returns an int32 device tensor (8, n_windows, ceil(n_kmers / 32)), the start matrix (`out`,
+        when given, is written instead; asynchronous)."""
+        import torch
+
+        ws = sample.as_struct() if hasattr(sample, "as_struct") else sample
+        ws = ws.sample if isinstance(ws, ACSegment) else ws
+        words = (int(n_kmers) + 31) // 32
+        if out is None:
+            out = torch.empty(max(positions_words(n_kmers, ws.n_windows), 1), dtype=torch.int32, device=hits.device)
+        p = lambda t: ctypes.cast(ctypes.c_void_p(t.data_ptr() if t is not None else 0), _lib.p32)  # noqa: E731
+        kp = ctypes.cast(ctypes.c_void_p(kmers.data_ptr() if kmers is not None else 0), ctypes.POINTER(ctypes.c_uint64))
+        check(self._L.ac_hit_start_positions_device(self._h, int(k), kp, int(n_kmers), ctypes.byref(ws), int(window_len),
+                                                    p(hits), p(pos), int(levels), p(out), ctypes.c_void_p(stream or 0)),
+              self._h)
+        return out[: positions_words(n_kmers, ws.n_windows)].view(8, int(ws.n_windows), words)
 
     def hit_position_profile(self, hits, pos, n_kmers: int, n_windows: int, levels: int, window_len: int, stream=None):
         """ac_hit_position_profile_device over a device hit matrix (`levels` planes) and its position
@@ -777,7 +857,7 @@ class ApproxCounter:
         return (ACSegment * len(segments))(*[s.as_struct() for s in segments])
 
     def count_device(self, k: int, segments, stream=None, accumulate: bool = False, window_len=None, hits=None,
-                     positions=None) -> None:
+                     positions=None, spans=None) -> None:
         """ac_error_count_device over DeviceSegment objects, or an array from
         segment_array (asynchronous).  window_len (one per segment): the samples'
         windows all have that length and sit back to back at ceil32 strides
@@ -785,7 +865,12 @@ class ApproxCounter:
         hits (one device tensor per segment, hits_words(...) int32 / uint32 words each; None for a segment
         without work): ac_window_hits_device -- the same launch also writes the windows' hit levels
         (window_len required, no accumulate).  positions (with hits; one device tensor per segment,
-        positions_words(...) words each): ac_window_positions_device -- and the match end positions."""
+        positions_words(...) words each): ac_window_positions_device -- and the match end positions.  spans (with
+        positions; one device tensor per segment, positions_words(...) words each): the span pass
+        (ac_hit_start_positions_device) is enqueued on the same stream after the launch, per segment with
+        work, and fills the match starts."""
+        if spans is not None and (hits is None or positions is None):
+            raise ValueError("spans come with hits and positions")
         arr = segments if isinstance(segments, ctypes.Array) else self.segment_array(segments)
         wp = None
         if window_len is not None:
@@ -816,6 +901,20 @@ class ApproxCounter:
                                                ctypes.c_void_p(stream or 0))
         if st:
             check(st, self._h)
+        if spans is not None:
+            if len(spans) != len(arr):
+                raise ValueError("one spans tensor per segment")
+            if window_len is None:
+                raise ValueError("spans need window_len")
+            for seg, L, h, p, t in zip(arr, wl, hits, positions, spans):
+                if seg.n_kmers and seg.sample.n_windows:
+                    st = self._L.ac_hit_start_positions_device(
+                        self._h, int(k), seg.kmers, seg.n_kmers, ctypes.byref(seg.sample), int(L),
+                        *[ctypes.cast(ctypes.c_void_p(x.data_ptr() if x is not None else 0), _lib.p32) for x in (h, p)],
+                        self.max_errors + 1, ctypes.cast(ctypes.c_void_p(t.data_ptr() if t is not None else 0), _lib.p32),
+                        ctypes.c_void_p(stream or 0))
+                    if st:
+                        check(st, self._h)
 
     def last_launch(self):
         w, wpw, g = ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_uint32()

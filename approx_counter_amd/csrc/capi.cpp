@@ -289,6 +289,7 @@ void ac_destroy(ac_ctx* ctx) {
     if (ctx->d_stage) (void)hipFree(ctx->d_stage);
     if (ctx->d_hits) (void)hipFree(ctx->d_hits);
     if (ctx->d_pos) (void)hipFree(ctx->d_pos);
+    if (ctx->d_start) (void)hipFree(ctx->d_start);
     if (ctx->d_cooc) (void)hipFree(ctx->d_cooc);
     if (ctx->d_cooc_io) (void)hipFree(ctx->d_cooc_io);
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
@@ -566,9 +567,11 @@ ac_status ac_count(ac_ctx* ctx, uint32_t k, const uint64_t* kmers, uint32_t n_km
 
 
 // ac_error_count_samples, and -- hits_host: one host matrix per job -- ac_window_hits_samples, and --
-// pos_host beside it -- ac_window_positions_samples.
+// pos_host beside it -- ac_window_positions_samples, and -- start_host beside both: the span pass over every
+// job's device matrices after the launch -- ac_window_spans_samples.
 static ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, uint32_t n_jobs,
-                               uint32_t* const* hits_host, uint32_t* const* pos_host = nullptr) {
+                               uint32_t* const* hits_host, uint32_t* const* pos_host = nullptr,
+                               uint32_t* const* start_host = nullptr) {
     if (!ctx) return fail(nullptr, AC_ERR_INVALID, "ctx is NULL");
     if (ac_status st = check_k(ctx, k)) return st;
     if (n_jobs > AC_MAX_JOBS) return fail(ctx, AC_ERR_INVALID, "too many jobs in one call (max 4)");
@@ -608,6 +611,7 @@ static ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* job
     size_t hits_bytes[AC_MAX_JOBS] = {};
     uint32_t* d_pos[AC_MAX_JOBS] = {};
     size_t pos_bytes[AC_MAX_JOBS] = {};
+    uint32_t* d_start[AC_MAX_JOBS] = {};
     if (hits_host) {
         bool live[AC_MAX_JOBS];
         for (uint32_t j = 0; j < n_jobs; ++j) live[j] = jobs[j].n_kmers && jobs[j].sample.n_windows;
@@ -626,18 +630,23 @@ static ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* job
                 pos_bytes[j] = sizeof(uint32_t) * (size_t)ac_window_positions_words(jobs[j].n_kmers, jobs[j].sample.n_windows);
                 if (live[j] && !pos_host[j])
                     return fail(ctx, AC_ERR_INVALID, "window positions: pos_host[j] is NULL for a job with work");
+                if (start_host && live[j] && !start_host[j])
+                    return fail(ctx, AC_ERR_INVALID, "match spans: start_host[j] is NULL for a job with work");
                 all_pos += align256(pos_bytes[j]);
             }
         AC_HIP(ctx, hipSetDevice(ctx->device));
         if (ac_status s2 = grow(ctx, &ctx->d_hits, &ctx->d_hits_cap, all)) return s2;
         if (pos_host)
             if (ac_status s2 = grow(ctx, &ctx->d_pos, &ctx->d_pos_cap, all_pos)) return s2;
+        if (pos_host && start_host)
+            if (ac_status s2 = grow(ctx, &ctx->d_start, &ctx->d_start_cap, all_pos)) return s2;
         size_t at = 0, at_pos = 0;
         for (uint32_t j = 0; j < n_jobs; ++j) {
             d_hits[j] = (uint32_t*)((char*)ctx->d_hits + at);
             at += align256(hits_bytes[j]);
             if (pos_host) {
                 d_pos[j] = (uint32_t*)((char*)ctx->d_pos + at_pos);
+                if (start_host) d_start[j] = (uint32_t*)((char*)ctx->d_start + at_pos);
                 at_pos += align256(pos_bytes[j]);
             }
         }
@@ -676,6 +685,15 @@ static ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* job
         for (uint32_t j = 0; j < n_jobs; ++j)
             if (jobs[j].n_kmers && jobs[j].sample.n_windows)
                 AC_HIP(ctx, hipMemcpyAsync(pos_host[j], d_pos[j], pos_bytes[j], hipMemcpyDeviceToHost, st));
+    if (hits_host && pos_host && start_host)
+        for (uint32_t j = 0; j < n_jobs; ++j)
+            if (jobs[j].n_kmers && jobs[j].sample.n_windows) {
+                // (hits_refusal has let only equal windows of 1..256 bases through: ulen[j] is their length)
+                if (ac_status rc = span_device(ctx, k, seg[j].kmers, jobs[j].n_kmers, &jobs[j].sample, ulen[j], d_hits[j],
+                                               d_pos[j], ctx->max_errors + 1u, d_start[j], st))
+                    return rc;
+                AC_HIP(ctx, hipMemcpyAsync(start_host[j], d_start[j], pos_bytes[j], hipMemcpyDeviceToHost, st));
+            }
     if (ac_status rc = ac_check(ctx, st)) return rc;  // synchronises the stream
     base = 0;
     for (uint32_t j = 0; j < n_jobs; ++j)
@@ -732,6 +750,17 @@ ac_status ac_window_positions_samples(ac_ctx* ctx, uint32_t k, const ac_sample_j
     if (n_jobs && !pos_host) return fail(ctx, AC_ERR_INVALID, "window positions: pos_host is NULL");
     static uint32_t* const none[AC_MAX_JOBS] = {};
     return count_samples(ctx, k, jobs, n_jobs, hits_host ? hits_host : none, pos_host ? pos_host : none);
+}
+
+ac_status ac_window_spans_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, uint32_t n_jobs,
+                                  uint32_t* const* hits_host, uint32_t* const* pos_host, uint32_t* const* start_host) {
+    if (!ctx) return fail(nullptr, AC_ERR_INVALID, "ctx is NULL");
+    if (n_jobs && !hits_host) return fail(ctx, AC_ERR_INVALID, "window hits: hits_host is NULL");
+    if (n_jobs && !pos_host) return fail(ctx, AC_ERR_INVALID, "window positions: pos_host is NULL");
+    if (n_jobs && !start_host) return fail(ctx, AC_ERR_INVALID, "match spans: start_host is NULL");
+    static uint32_t* const none[AC_MAX_JOBS] = {};
+    return count_samples(ctx, k, jobs, n_jobs, hits_host ? hits_host : none, pos_host ? pos_host : none,
+                         start_host ? start_host : none);
 }
 
 ac_status ac_hit_position_profile_device(ac_ctx* ctx, const uint32_t* hits, const uint32_t* pos, uint32_t n_kmers,

@@ -1,5 +1,5 @@
 // ctx.h -- the context and the helpers shared by the C-ABI translation units (capi.cpp,
-// count_launch.cpp, capi_exact.cpp, capi_comm.cpp, capi_cooc.cpp, capi_cross.cpp, jobs_stage.cpp).  Private to the library:
+// count_launch.cpp, capi_exact.cpp, capi_comm.cpp, capi_cooc.cpp, capi_cross.cpp, capi_span.cpp, jobs_stage.cpp).  Private to the library:
 // nothing declared here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -35,6 +35,9 @@ struct ac_ctx {
     // ac_window_positions_samples / ac_window_positions_jobs: the jobs' device position matrices, likewise
     void* d_pos = nullptr;
     size_t d_pos_cap = 0;
+    // ac_window_spans_samples: the jobs' device start matrices, likewise
+    void* d_start = nullptr;
+    size_t d_start_cap = 0;
     // ac_hit_cooccurrence*: the transposed planes the product reads (grow-only; stream-ordered like the
     // count scratch), and the host-buffer call's device matrix and result, back to back
     void* d_cooc = nullptr;
@@ -229,6 +232,11 @@ struct CountLaunch {
     const uint32_t* mat_windows = nullptr;
 };
 ac_status launch(ac_ctx* ctx, const CountLaunch& rq);
+
+// --- capi_span.cpp: ac_hit_start_positions_device's checks and launch (the samples route ends here too)
+ac_status span_device(ac_ctx* ctx, uint32_t k, const uint64_t* kmers, uint32_t n_kmers, const ac_windows* sample,
+                      uint32_t window_len, const uint32_t* hits, const uint32_t* pos, uint32_t levels, uint32_t* start_out,
+                      hipStream_t stream);
 
 // --- capi_comm.cpp
 void comm_destroy(ac_ctx* ctx);  // the context's communicator, if it has one (ac_destroy)

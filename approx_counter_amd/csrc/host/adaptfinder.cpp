@@ -17,6 +17,10 @@
 //   --positions     beside every <out>_<run>.<end> file a <out>_<run>.<end>.positions file: per k-mer, in the
 //                   same order, for every base 1..L of the sampled windows how many of the windows within E
 //                   edits have their best occurrence ending there (ac_window_positions_samples)
+//   --spans         beside every <out>_<run>.<end> file a <out>_<run>.<end>.starts and a <out>_<run>.<end>.lengths
+//                   file: per k-mer, in the same order, for every base 1..L how many of the windows within E edits
+//                   have their best occurrence starting there, and for every occurrence length k - E .. k + E how
+//                   many have that length (ac_window_spans_samples)
 //   --cooccurrence  beside every <out>_<run>.<end> file a <out>_<run>.<end>.cooc file: per k-mer, in the same
 //                   order, for every k-mer of the file how many sampled windows hold the two together within
 //                   E edits (two of the reference's bitfields at once; ac_hit_cooccurrence)
@@ -104,6 +108,13 @@ const Opt OPTS[] = {
      "k-mer and, for every base 1 to L of the sampled windows, the number of windows holding it within max-errors "
      "edits whose leftmost best occurrence ends at that base (they sum to the last column of its .levels line). "
      "Same needs as --levels, with which it can be combined."},
+    {"", "spans", Kind::Flag,
+     "[MI355X build] also write <out>_<run>.<end>.starts and <out>_<run>.<end>.lengths: one line per k-mer of the main "
+     "file, in its order. A .starts line is the k-mer and, for every base 1 to L of the sampled windows, the number of "
+     "windows holding it within max-errors edits whose best occurrence (the shortest one ending where .positions says) "
+     "starts at that base; a .lengths line is the k-mer and the number of those windows by occurrence length, from "
+     "k - max-errors to k + max-errors. Both sum to the last column of its .levels line. Same needs as --levels, with "
+     "which and with --positions it can be combined."},
     {"", "cooccurrence", Kind::Flag,
      "[MI355X build] also write <out>_<run>.<end>.cooc: one line per k-mer of the main file, in its order, the "
      "k-mer and, for every k-mer of the main file in the same order, the number of sampled windows holding both "
@@ -319,6 +330,49 @@ bool export_positions(const pair_vector& ranked, const std::vector<uint64_t>& km
     return std::fclose(f) == 0;
 }
 
+// --spans: two files, one line per k-mer of `ranked` each.  .starts: the k-mer and window_len counts -- the
+// position profile's fold (export_positions) over the job's START matrix, whose stored value is the 0-based
+// start, so column p + 1 counts the windows whose best occurrence starts at base p + 1.  .lengths: the k-mer
+// and 2 E + 1 counts, the windows by end - start = k - E .. k + E, from the two matrices together.
+bool export_spans(const pair_vector& ranked, const std::vector<uint64_t>& kmers, const std::vector<uint32_t>& hits,
+                  const std::vector<uint32_t>& pos, const std::vector<uint32_t>& start, uint32_t n_windows, uint32_t levels,
+                  uint32_t window_len, uint32_t k, const std::string& starts_path, const std::string& lengths_path) {
+    if (!export_positions(ranked, kmers, hits, start, n_windows, levels, window_len, k, starts_path)) return false;
+    const uint32_t n = (uint32_t)kmers.size(), words = (n + 31u) / 32u, E = levels - 1u, bins = 2u * E + 1u;
+    const size_t plane = (size_t)n_windows * words;
+    std::vector<uint32_t> prof((size_t)n * bins, 0u);
+    for (uint32_t w = 0; w < n_windows; ++w)
+        for (uint32_t col = 0; col < words; ++col) {
+            const size_t at = (size_t)w * words + col;
+            const uint32_t left = n - 32u * col;
+            uint32_t m = hits[(size_t)E * plane + at] & (left >= 32u ? ~0u : (1u << left) - 1u);
+            if (!m) continue;
+            uint32_t p[acamd::bs::POS_PLANES], s[acamd::bs::POS_PLANES];
+            for (int b = 0; b < acamd::bs::POS_PLANES; ++b) {
+                p[b] = pos[(size_t)b * plane + at];
+                s[b] = start[(size_t)b * plane + at];
+            }
+            for (; m; m &= m - 1u) {
+                const uint32_t j = (uint32_t)__builtin_ctz(m);
+                const uint32_t len = acamd::bs::pos_get(p, j) + 1u - acamd::bs::pos_get(s, j);  // (end - start)
+                if (len + E >= k && len + E - k < bins) ++prof[(size_t)(32u * col + j) * bins + (len + E - k)];
+            }
+        }
+    std::map<uint64_t, uint32_t> index;  // (the exact count's k-mers are distinct)
+    for (uint32_t c = 0; c < n; ++c) index.emplace(kmers[c], c);
+    std::FILE* f = std::fopen(lengths_path.c_str(), "wb");
+    if (!f) return false;
+    std::string line;
+    for (const auto& kv : ranked) {
+        const uint32_t c = index.at(kv.first);
+        line = int2dna(kv.first, k);
+        for (uint32_t b = 0; b < bins; ++b) line += '\t' + std::to_string(prof[(size_t)c * bins + b]);
+        line += '\n';
+        std::fwrite(line.data(), 1, line.size(), f);
+    }
+    return std::fclose(f) == 0;
+}
+
 // --cooccurrence: one line per k-mer of `ranked`, the k-mer and one count per k-mer of `ranked` in the same
 // order -- `cooc` is the n x n result of ac_hit_cooccurrence over the job's top level plane, candidate c =
 // kmers[c], permuted here into the main file's order.
@@ -454,6 +508,7 @@ int main(int argc, char const** argv) {
     const bool host_exact = args.val.count("host-exact") > 0;
     const bool levels = args.val.count("levels") > 0;
     const bool positions = args.val.count("positions") > 0;
+    const bool spans = args.val.count("spans") > 0;
     const bool cooccurrence = args.val.count("cooccurrence") > 0;
     const bool paired = args.val.count("paired-sample") > 0;
     const bool cross = args.val.count("cross-cooccurrence") > 0;
@@ -510,9 +565,13 @@ int main(int argc, char const** argv) {
     // (ac_window_hits_samples); what only the sample can tell -- read ends of unequal length -- the
     // library refuses when the count is asked for.
     // --positions: the same kernels' sibling family, the same constraints and messages.
+    // --spans: a pass over the positions call's matrices, so the same again.
     // --cooccurrence, --cross-cooccurrence: reductions of the same hit matrices, so the same again.
-    const std::pair<const char*, bool> hit_flags[] = {
-        {"--levels", levels}, {"--positions", positions}, {"--cooccurrence", cooccurrence}, {"--cross-cooccurrence", cross}};
+    const std::pair<const char*, bool> hit_flags[] = {{"--levels", levels},
+                                                      {"--positions", positions},
+                                                      {"--spans", spans},
+                                                      {"--cooccurrence", cooccurrence},
+                                                      {"--cross-cooccurrence", cross}};
     for (const auto& hf : hit_flags) {
         const char* flag = hf.first;
         if (!hf.second) continue;
@@ -608,6 +667,9 @@ int main(int argc, char const** argv) {
             // --positions: the positions call, which yields the counts and the levels as well
             std::vector<std::vector<uint32_t>> pos(pending.size());
             std::vector<uint32_t*> pos_p(pending.size());
+            // --spans: the spans call, which yields all of that and the start matrices
+            std::vector<std::vector<uint32_t>> start(pending.size());
+            std::vector<uint32_t*> start_p(pending.size());
             // --cooccurrence: the hits call as well, then the top level plane's co-occurrence
             std::vector<std::vector<uint32_t>> cooc(pending.size());
             // --cross-cooccurrence: the hits call as well, then the two ends' top level planes against each other
@@ -618,18 +680,24 @@ int main(int argc, char const** argv) {
                 const bool on_device = !host_exact && dev.shards == 1;  // the samples uploaded for the exact count
                 for (size_t e = 0; e < pending.size(); ++e)
                     jobs[e].sample = on_device ? pending[e].dsample : view(pending[e].img);
-                if (levels || positions || cooccurrence || cross)
+                if (levels || positions || spans || cooccurrence || cross)
                     for (size_t e = 0; e < pending.size(); ++e) {
                         hits[e].assign((size_t)ac_window_hits_words(jobs[e].n_kmers, jobs[e].sample.n_windows,
                                                                     (uint32_t)max_errors) + 1, 0u);
                         hits_p[e] = hits[e].data();
-                        if (positions) {
+                        if (positions || spans) {
                             pos[e].assign((size_t)ac_window_positions_words(jobs[e].n_kmers, jobs[e].sample.n_windows) + 1, 0u);
                             pos_p[e] = pos[e].data();
                         }
+                        if (spans) {
+                            start[e].assign(pos[e].size(), 0u);
+                            start_p[e] = start[e].data();
+                        }
                     }
                 const ac_status st =
-                    positions   ? ac_window_positions_samples(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size(),
+                    spans       ? ac_window_spans_samples(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size(), hits_p.data(),
+                                                          pos_p.data(), start_p.data())
+                    : positions ? ac_window_positions_samples(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size(),
                                                               hits_p.data(), pos_p.data())
                     : levels || cooccurrence || cross
                         ? ac_window_hits_samples(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size(), hits_p.data())
@@ -684,6 +752,14 @@ int main(int argc, char const** argv) {
                                       (uint32_t)k, path + ".positions")) {
                     std::cerr << error_pref + "Failed to export the match end positions" << std::endl;
                     std::cerr << "Path: " << path + ".positions" << std::endl;
+                    return false;
+                }
+                if (spans &&
+                    !export_spans(sorted_error_count, km[e], hits[e], pos[e], start[e], jobs[e].sample.n_windows,
+                                  (uint32_t)max_errors + 1, pending[e].img.length.empty() ? 0u : pending[e].img.length[0],
+                                  (uint32_t)k, path + ".starts", path + ".lengths")) {
+                    std::cerr << error_pref + "Failed to export the match spans" << std::endl;
+                    std::cerr << "Path: " << path + ".starts" << std::endl;
                     return false;
                 }
                 if (cooccurrence && !export_cooccurrence(sorted_error_count, km[e], cooc[e], (uint32_t)k, path + ".cooc")) {

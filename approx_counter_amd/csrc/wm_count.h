@@ -350,6 +350,12 @@ hipError_t launch_hit_cooccurrence(const uint32_t* hits, uint32_t n_kmers, uint3
 // word stored once
 hipError_t launch_hit_window_counts(const uint32_t* hits, uint32_t n_kmers, uint32_t n_windows, uint32_t levels,
                                     uint32_t* window_counts, hipStream_t stream);
+// hit_span.hip: the start matrix (hit_span.h: eight planes of the hit matrix's shape) of a hit matrix of
+// `levels` planes and its position matrix over equal windows of window_len bases (1..256) at ceil32 strides
+// of the image codes / nmask; every word of start stored once
+hipError_t launch_hit_start_positions(uint32_t k, const uint64_t* kmers, uint32_t n_kmers, const uint32_t* codes,
+                                      const uint32_t* nmask, uint32_t n_windows, uint32_t window_len, const uint32_t* hits,
+                                      const uint32_t* pos, uint32_t levels, uint32_t* start, hipStream_t stream);
 
 // Waves of the count kernel for pattern pack P that fit on the device at once.
 hipError_t resident_waves(uint32_t P, bool staged, int cu_count, uint32_t* waves);

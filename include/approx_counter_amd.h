@@ -545,6 +545,64 @@ ac_status ac_hit_position_profile_device(ac_ctx* ctx, const uint32_t* hits, cons
                                          void* hip_stream);
 
 /*
+ * Match spans: where in its window each k-mer's best occurrence STARTS
+ * (additive exports of ABI 8).  The end positions above give one edge of an
+ * occurrence; for an end window, whose adapter runs from some base to the
+ * read's last one, the informative edge is the other.  With w a window of L
+ * bases, c a k-mer, E the budget, d = d(c, w) <= E, pos = pos(c, w) as above
+ * (the exclusive end of the leftmost occurrence at distance d), ed the plain
+ * global edit distance and an N of the window matching nothing,
+ *     start(c, w) = max { s : ed(c, w[s, pos)) = d }    0 <= start <= pos - (k - d)
+ *     len(c, w)   = pos - start                         k - d <= len <= k + d
+ * the SHORTEST substring ending at pos at the best distance.  The end rule
+ * already prefers the shorter occurrence at the right edge (ACGT in ..ACGA..
+ * ends after ACG); the left edge does the same: a first base substituted in
+ * the text is left out of the span, not covered as a mismatch.  Such an s
+ * always exists, because e(pos) = d means exactly that.
+ * A start matrix has exactly the layout of a position matrix: eight bit planes
+ * of the hit matrix's shape,
+ *     start_m[(b * n_windows + w) * words + c / 32], bit c % 32
+ *         = bit b of start(c, w)            (the value as it is, 0..255)
+ * 0 in every plane where d > E, for candidates >= n_kmers and in skipped
+ * windows.  Every word is written by the pass: the caller clears nothing.  Its
+ * size is ac_window_positions_words, and ac_hit_position_profile_device works
+ * on it unchanged: its index p - 1 is then the start offset.
+ *   ac_hit_start_positions_device
+ *       the pass alone: from the device k-mers, the device sample (equal
+ *       windows of window_len bases at ceil32(window_len)-base strides: codes
+ *       and nmask are read, bases below window_len only; start / length are
+ *       not), a device hit matrix of `levels` planes and its position matrix,
+ *       into start_out (device memory).  Asynchronous on hip_stream.  Its work
+ *       follows the hit pairs, not all pairs: a bit-vector alignment of the
+ *       reversed k-mer against the reversed text before pos, at most
+ *       k + levels - 1 steps a hit.  Runs on any context, whichever kernel wrote
+ *       the matrices and whatever AC_BITSLICE is; an ac_create_multi context
+ *       uses its first device.  Input planes may hold anything: a pair whose
+ *       planes are inconsistent (a stored position past window_len, no
+ *       substring ending there at the plane's distance, a level bit without the
+ *       top level's) gets 0 bits, and nothing outside the windows is read.
+ *       AC_ERR_INVALID before anything is enqueued, the constraint in
+ *       ac_last_error, for: a NULL ctx; k outside 2..32; levels outside 1..4 or
+ *       levels >= k (an occurrence could then be empty); window_len outside
+ *       1..256; n_windows x ceil32(window_len) past n_bases; a NULL sample; a
+ *       NULL hits, pos, codes, nmask, kmers or output when there is work.  The
+ *       context stays usable.  n_kmers = 0 or n_windows = 0 is no work.
+ *   ac_window_spans_samples
+ *       ac_window_positions_samples followed, per job with work, by the pass on
+ *       the context's stream over the resident sample and the context's device
+ *       matrices, then copied out (start_host[j], ac_window_positions_words u32).
+ *       Synchronous.  Refuses exactly what ac_window_positions_samples refuses,
+ *       plus a NULL start matrix for a job with work.
+ * Not built: spans from the jobs stage (ac_window_*_jobs*), whose image keeps N
+ * in inline records, and from word-parallel launches, which write no hit matrix.
+ */
+ac_status ac_hit_start_positions_device(ac_ctx* ctx, uint32_t k, const uint64_t* kmers, uint32_t n_kmers,
+                                        const ac_windows* sample, uint32_t window_len, const uint32_t* hits,
+                                        const uint32_t* pos, uint32_t levels, uint32_t* start_out, void* hip_stream);
+ac_status ac_window_spans_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, uint32_t n_jobs,
+                                  uint32_t* const* hits_host, uint32_t* const* pos_host, uint32_t* const* start_host);
+
+/*
  * Hit levels and end positions from the jobs stage (additive exports of ABI 8):
  * ac_error_count_jobs / _submit -- Dna5 windows in, the whole errorCount stage --
  * that also return the matrices above, from the same one launch: packing still

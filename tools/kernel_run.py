@@ -18,6 +18,10 @@ levels, DESIGN.md 4e "Hit levels") and prints the bytes of the matrices beside t
 times ac_hit_level_counts_device over the first segment's matrix and prints the rate its bytes were read at.
 --positions runs the hits-and-positions kernels instead (ac_window_positions_device, DESIGN.md 4e "Match end
 positions"); --profile then times ac_hit_position_profile_device over the first segment's two matrices.
+--spans (with --positions) then times the span pass (ac_hit_start_positions_device, DESIGN.md 4e "Match spans") over
+every segment's matrices on resident input, in rounds interleaved with the hits-and-positions launch that produces
+its input, and prints the top level plane's hit density; --random-windows replaces every window by random bases (no
+planted occurrence: a density near 0, to see whether the pass's time follows the hits or the pairs).
 --cooc (with --hits or --positions) then times the co-occurrence of the first segment's top level plane on the
 resident matrix (ac_hit_cooccurrence_device, DESIGN.md 4e "Co-occurrence"): the transposition and the product on
 their own (ac_testing_hit_cooccurrence_stages) and the whole call, beside the level counter on the same plane and
@@ -60,6 +64,11 @@ def main():
                     help="the hits-and-positions kernels (ac_window_positions_device); implies --hits")
     ap.add_argument("--profile", action="store_true",
                     help="with --positions: also time ac_hit_position_profile_device over the first segment's matrices")
+    ap.add_argument("--spans", action="store_true",
+                    help="with --positions: also time ac_hit_start_positions_device over every segment's matrices, "
+                         "interleaved with the launch, and print the top plane's hit density")
+    ap.add_argument("--random-windows", action="store_true",
+                    help="replace every window by random bases of the same length (no planted occurrence)")
     ap.add_argument("--cooc", action="store_true",
                     help="with --hits / --positions: also time ac_hit_cooccurrence_device over the first segment's top "
                          "level plane: transposition, product and the whole call")
@@ -76,6 +85,12 @@ def main():
     sys.argv = ["bench.py", "--config", a.config] + (["--k", str(a.k)] if a.k else [])
     args = bench.parse()
     wl, _ = bench.build_workload(args, 0, 1)
+    if a.random_windows:
+        import numpy as np
+
+        rng = np.random.default_rng(args.seed)
+        for e in ("start", "end"):
+            wl[e]["windows"] = [rng.integers(0, 4, size=len(w), dtype=np.uint8) for w in wl[e]["windows"]]
     if a.staged:
         from approx_counter_amd._lib import load
 
@@ -233,6 +248,58 @@ def main():
                   + ", ".join(f"{k} {v:.4f} ms" for k, v in ms.items())
                   + f" per call; cross product {per_c * 1e3:.4f} us per tile ({tiles} tiles), gram product "
                   f"{per_g * 1e3:.4f} us per tile pair ({pairs} pairs), ratio {per_c / per_g:.3f}")
+        if a.positions and a.spans:
+            if wlen is None:
+                sys.exit("--spans needs equal windows")
+            E, lv = a.max_errors, a.max_errors + 1
+            starts = [torch.empty(max(w, 1), dtype=torch.int32, device="cuda") for w in pwords]
+            live = [i for i, s in enumerate(segs) if s.n_kmers and s.n_windows]
+
+            def the_pass():
+                for i in live:
+                    c.hit_start_positions(args.k, segs[i].kmers, segs[i].n_kmers, segs[i], wlen[i], hits[i], pos[i], lv,
+                                          out=starts[i])
+
+            rounds, t_launch, t_pass = 5, [], []
+            for r in range(rounds):  # a round: the launch's calls, then the pass's, on the same box minutes apart at most
+                for call, into in ((lambda: c.count_device(args.k, arr, window_len=wlen, hits=hits, positions=pos), t_launch),
+                                   (the_pass, t_pass)):
+                    for i in range(a.warmup + a.launches):
+                        if i == a.warmup:
+                            t0.record()
+                        call()
+                    t1.record()
+                    torch.cuda.synchronize()
+                    into.append(t0.elapsed_time(t1) / a.launches)
+            c.check()
+            pairs = hit_pairs = steps = 0
+            j = torch.arange(32, device="cuda", dtype=torch.int32)[:, None]
+
+            def values(planes):  # (8, words) plane words -> (32, words) values, bit j of a word its row j
+                v = torch.zeros((32, planes.shape[1]), dtype=torch.int32, device="cuda")
+                for b in range(8):
+                    v |= ((planes[b][None, :] >> j) & 1) << b
+                return v
+
+            for i in live:
+                s, words_i = segs[i], (segs[i].n_kmers + 31) // 32
+                top = hits[i][E * s.n_windows * words_i: lv * s.n_windows * words_i]
+                st, pl = starts[i][: pwords[i]].view(8, -1), pos[i][: pwords[i]].view(8, -1)
+                assert not bool((st & ~top[None, :]).any()), "a start bit without a hit"
+                mask = ((top[None, :] >> j) & 1).bool()
+                ln = (values(pl) + 1 - values(st))[mask]
+                # every hit has a span, of a length the budget allows
+                assert bool(((ln >= args.k - E) & (ln <= args.k + E)).all()), "an occurrence length outside k - E .. k + E"
+                hit_pairs += int(mask.sum())
+                pairs += s.n_kmers * s.n_windows
+                steps += int(ln.sum())
+            ml, mp = sum(t_launch) / rounds, sum(t_pass) / rounds
+            ops = steps * 30 + hit_pairs * 35  # (hit_span.h: about 30 integer ops a column, 35 to split the k-mer)
+            print(f"span pass, k {args.k} E {E}: top plane density {hit_pairs / max(pairs, 1) * 100:.3f} % "
+                  f"({hit_pairs} of {pairs} pairs); pass {mp:.4f} ms, launch {ml:.4f} ms, ratio {mp / ml:.3f} "
+                  f"(rounds: pass {', '.join(f'{x:.4f}' for x in t_pass)}; launch {', '.join(f'{x:.4f}' for x in t_launch)}); "
+                  f"op model {steps} columns = {ops:.3e} lane-ops = {ops / bench.VALU_PEAK_OPS * 1e3:.5f} ms at the VALU "
+                  f"peak, {ops / bench.VALU_PEAK_OPS * 1e3 / mp * 100:.2f} % of the pass's time")
         if a.positions and a.profile:
             s0 = segs[0]
             for i in range(a.warmup + a.launches):
