@@ -256,9 +256,11 @@ __device__ __forceinline__ void bs_body(const LaunchArgs& a, BsLds<K>& lds) {
     // every lane loads its window's slot (up to 64 bytes; the lanes of a window load the same lines), the
     // window's first lane stores it into the wave's text buffer, and every chunk of 16 bases reads its
     // one code word from there.  Two buffers: the next row's text is fetched while this row is counted.
-    // A lane without a window (a partial last row) loads from an offset past any image's range check,
-    // i.e. zeros without a memory access.
+    // A lane without a window (a partial last row) loads from an offset past the range check of every image
+    // the host accepts -- AC_MAX_IMAGE_BASES keeps an image's code bytes below it (wm_count.h) -- i.e. zeros
+    // without a memory access; and no window's slot offset equals it, so it also says "no window" below.
     constexpr uint32_t NO_WINDOW = 0xffffff00u;
+    static_assert(AC_MAX_IMAGE_BASES / 4u <= NO_WINDOW, "an accepted image's code bytes end below NO_WINDOW");
     auto slot_off = [&](uint32_t rr) __attribute__((always_inline)) {
         const uint32_t w = rr * wpr + wl;
         return w < seg_nw ? w * sbytes : NO_WINDOW;

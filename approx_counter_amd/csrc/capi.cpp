@@ -108,7 +108,7 @@ ac_status h2d_staged(ac_ctx* ctx, int n, const void* const* src, const size_t* s
 ac_status check_sample(ac_ctx* ctx, const ac_windows* s) {
     if (!s) return fail(ctx, AC_ERR_INVALID, "sample is NULL");
     if (s->n_bases % 32 || s->n_bases >= AC_MAX_IMAGE_BASES)
-        return fail(ctx, AC_ERR_INVALID, "sample n_bases must be a multiple of 32 below 2^34");
+        return fail(ctx, AC_ERR_INVALID, "sample n_bases must be a multiple of 32 below 2^34 - 4096");
     if (s->n_windows && (!s->codes || !s->nmask || !s->start || !s->length))
         return fail(ctx, AC_ERR_INVALID, "sample has a NULL array");
     return AC_OK;

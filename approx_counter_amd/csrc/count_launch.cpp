@@ -120,7 +120,7 @@ ac_status launch(ac_ctx* ctx, const CountLaunch& rq) {
         if (equal && (uint64_t)s.sample.n_windows * ((rq.ulen[i] + 31ull) & ~31ull) > s.sample.n_bases)
             return fail(ctx, AC_ERR_INVALID, "equal windows reach past n_bases");
         if (s.sample.n_bases % 32 || s.sample.n_bases >= AC_MAX_IMAGE_BASES)
-            return fail(ctx, AC_ERR_INVALID, "sample n_bases must be a multiple of 32 below 2^34");
+            return fail(ctx, AC_ERR_INVALID, "sample n_bases must be a multiple of 32 below 2^34 - 4096");
         // The count hand-off adds (1 << 32) + sum into 64-bit slots (wm_count.hip): a candidate's sum,
         // at most 3 per window (4 at an edit budget of 3), must stay below 2^32 or its carry would count
         // as an arrival and the slot would never see its last workgroup.

@@ -7,8 +7,12 @@
 #define AC_QUEUE_LINE 32  // u32 per queue counter: one 128-B line each (no false sharing between counters)
 #define AC_MAX_PACK 4    // candidates interleaved per 32-bit lane word (P = min(32/k, 4))
 // Largest window image (bases, exclusive): the count kernel reads it through buffer descriptors whose
-// byte offsets and sizes are 32-bit (2 bits per base: 2^34 bases = 4 GiB of code words).
-#define AC_MAX_IMAGE_BASES (1ull << 34)
+// byte offsets and sizes are 32-bit (2 bits per base: 2^34 bases = 4 GiB of code words).  4096 bases
+// (1 KiB of code words) below 2^34: the bit-sliced kernel marks a lane without a window with the slot
+// offset 0xffffff00 (bs_count.inc NO_WINDOW), which has to lie past every image's range check together
+// with the 64 bytes a lane loads from there on -- in an image of more than 2^34 - 1024 bases it was the
+// offset of a real window, which the kernel then took for none (not counted, its hit words not written).
+#define AC_MAX_IMAGE_BASES ((1ull << 34) - 4096ull)
 #ifndef AC_WAVES_PER_BLOCK
 #define AC_WAVES_PER_BLOCK 4  // waves per workgroup, all on one candidate group (shared ~Eq table, counts summed in LDS)
 #endif
