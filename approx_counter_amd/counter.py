@@ -151,6 +151,35 @@ def cross_cooccurrence_words(n_a: int, n_b: int, levels: int = 1) -> int:
     return int(levels) * int(n_a) * int(n_b)
 
 
+def flank_words(n_kmers: int, depth: int) -> int:
+    """ac_hit_flank_words: the u32 words of a flank profile, 2 sides x n_kmers x depth x 5 symbols."""
+    return 2 * int(n_kmers) * int(depth) * 5
+
+
+def flank_consensus(profile, min_windows: int = 1, min_share: float = 0.5) -> list:
+    """The majority extension of every k-mer from its flank profile (uint32 (2, n_kmers, D, 5): side 0 = the
+    bases after the occurrence's end, 1 = before its start, nearest first; A C G T N).  Returns one
+    (left, right) pair of strings per k-mer, the left one in reading order (its last base is the one just
+    before the occurrence).  A side is extended from the nearest column while the column's total (N
+    included) is at least min_windows and its largest A/C/G/T count is more than min_share of the total; it
+    stops at the first column that fails.  Pure numpy."""
+    prof = np.asarray(profile)
+    if prof.ndim != 4 or prof.shape[0] != 2 or prof.shape[3] != 5:
+        raise ValueError("flank profile must be (2, n_kmers, depth, 5)")
+    prof = prof.astype(np.int64)
+    total = prof.sum(axis=3)
+    best = prof[..., :4].argmax(axis=3)
+    top = prof[..., :4].max(axis=3)
+    ok = (total >= max(int(min_windows), 1)) & (top > float(min_share) * total)
+    n = np.where(ok.all(axis=2), ok.shape[2], (~ok).argmax(axis=2))  # the columns before the first failing one
+    out = []
+    for c in range(prof.shape[1]):
+        right = "".join("ACGT"[b] for b in best[0, c, : n[0, c]])
+        left = "".join("ACGT"[b] for b in best[1, c, : n[1, c]])[::-1]
+        out.append((left, right))
+    return out
+
+
 def unpack_positions(planes, hit_E, n_kmers: int) -> np.ndarray:
     """A position matrix's values: `planes` is (8, n_windows, words) uint32, plane b holding bit b of
     pos - 1; `hit_E` is bool (n_windows, n_kmers), the pairs within the budget (level E of the hit
@@ -185,7 +214,7 @@ class WindowHits:
     window_hits(..., spans=True) the match starts as well (ac_window_spans_samples)."""
 
     def __init__(self, counts, levels, n_kmers: int, planes=None, window_len: int = 0, counter=None, starts=None,
-                 k: int = 0):
+                 k: int = 0, flanks=None):
         self.counts = counts
         self.levels = np.asarray(levels, dtype=np.uint32)  # (E + 1, n_windows, words)
         self.n_kmers = int(n_kmers)
@@ -193,7 +222,16 @@ class WindowHits:
         self.starts = None if starts is None else np.asarray(starts, dtype=np.uint32)  # (8, n_windows, words)
         self.window_len = int(window_len)
         self.k = int(k)
+        self.flanks = None if flanks is None else np.asarray(flanks, dtype=np.uint32)  # (2, n_kmers, D, 5)
         self._counter = counter
+
+    def flank_profile(self) -> np.ndarray:
+        """uint32 (2, n_kmers, D, 5): per k-mer the windows (within E edits) by the base -- A C G T N -- at each
+        of the D bases after the best occurrence's end (side 0) and before its start (side 1), nearest first;
+        a base outside the window is not counted (ac_window_flanks_samples)."""
+        if self.flanks is None:
+            raise ValueError("no flank profile: ask window_hits(..., flanks=D)")
+        return self.flanks
 
     def start_positions(self) -> np.ndarray:
         """int16 (n_windows, n_kmers): where the best occurrence starts (0-based, inclusive: the shortest
@@ -626,7 +664,7 @@ class ApproxCounter:
         """ac_error_count_samples: [(kmers, device sample from upload_sample), ...], one fused launch."""
         return self._sample_jobs(self._L.ac_error_count_samples, k, parts)
 
-    def window_hits(self, k: int, parts, positions: bool = False, spans: bool = False) -> list:
+    def window_hits(self, k: int, parts, positions: bool = False, spans: bool = False, flanks: int = 0) -> list:
         """ac_window_hits_samples: [(kmers, PackedSample), ...] (up to 4 parts, e.g. both read ends) are
         uploaded into the context's sample slots and counted in one fused launch that also writes every
         window's hit levels; returns one WindowHits per part.  Only where the bit-sliced kernel counts
@@ -634,11 +672,12 @@ class ApproxCounter:
         edit budget; anything else raises (AC_ERR_INVALID).  positions: ac_window_positions_samples -- every
         WindowHits also holds the match end positions (.end_positions(), .position_profile()).  spans (implies
         positions): ac_window_spans_samples -- and the match starts (.start_positions(), .span_lengths(),
-        .length_profile(), .start_profile())."""
+        .length_profile(), .start_profile()).  flanks = D in 1..32 (implies spans): ac_window_flanks_samples --
+        and the flank profile of D bases (.flank_profile())."""
         if not hasattr(self._L, "ac_window_hits_samples"):
             raise _lib.ApproxCounterError(_lib.AC_ERR_INVALID, "this build of the library has no ac_window_hits_samples")
-        if positions or spans:
-            return self._window_positions(k, parts, spans)
+        if positions or spans or flanks:
+            return self._window_positions(k, parts, spans or bool(flanks), int(flanks))
         E = self.max_errors
         keep, arr, mats = [], [], []
         for slot, (km, smp) in enumerate(parts):
@@ -657,33 +696,42 @@ class ApproxCounter:
                            counter=self)
                 for (km, c, nw), m in zip(keep, mats)]
 
-    def _window_positions(self, k: int, parts, spans: bool = False) -> list:
-        name = "ac_window_spans_samples" if spans else "ac_window_positions_samples"
+    def _window_positions(self, k: int, parts, spans: bool = False, flanks: int = 0) -> list:
+        name = "ac_window_flanks_samples" if flanks else "ac_window_spans_samples" if spans else "ac_window_positions_samples"
         if not hasattr(self._L, name):
             raise _lib.ApproxCounterError(_lib.AC_ERR_INVALID, f"this build of the library has no {name}")
         E = self.max_errors
-        keep, arr, mats, planes, starts = [], [], [], [], []
+        keep, arr, mats, planes, starts, profs = [], [], [], [], [], []
         for slot, (km, smp) in enumerate(parts):
             km = np.ascontiguousarray(np.asarray(km, dtype=np.uint64))
             c = np.zeros(max(km.size, 1), dtype=np.uint64)
             mats.append(np.full(max(hits_words(km.size, smp.n_windows, E), 1), 0xFFFFFFFF, dtype=np.uint32))
             planes.append(np.full(max(positions_words(km.size, smp.n_windows), 1), 0xFFFFFFFF, dtype=np.uint32))
             starts.append(np.full(max(positions_words(km.size, smp.n_windows), 1), 0xFFFFFFFF, dtype=np.uint32))
+            profs.append(np.full(max(flank_words(km.size, flanks), 1), 0xFFFFFFFF, dtype=np.uint32))
             keep.append((km, c, smp.n_windows, int(smp.length[0]) if smp.n_windows else 0))
             arr.append(ACSampleJob(_ptr(km if km.size else np.zeros(1, np.uint64), ctypes.c_uint64), int(km.size),
                                    self.upload_sample(smp, slot), _ptr(c, ctypes.c_uint64)))
         a = (ACSampleJob * len(arr))(*arr)
         hp = (_lib.p32 * len(arr))(*[_ptr(m, ctypes.c_uint32) for m in mats])
         pp = (_lib.p32 * len(arr))(*[_ptr(m, ctypes.c_uint32) for m in planes])
-        if spans:
+        if flanks:
+            sp = (_lib.p32 * len(arr))(*[_ptr(m, ctypes.c_uint32) for m in starts])
+            fp = (_lib.p32 * len(arr))(*[_ptr(m, ctypes.c_uint32) for m in profs])
+            check(self._L.ac_window_flanks_samples(self._h, int(k), a, len(arr), int(flanks), hp, pp, sp, fp), self._h)
+        elif spans:
             sp = (_lib.p32 * len(arr))(*[_ptr(m, ctypes.c_uint32) for m in starts])
             check(self._L.ac_window_spans_samples(self._h, int(k), a, len(arr), hp, pp, sp), self._h)
         else:
             check(self._L.ac_window_positions_samples(self._h, int(k), a, len(arr), hp, pp), self._h)
         shape = lambda m, km, nw: m[: positions_words(km.size, nw)].reshape(8, nw, (km.size + 31) // 32)  # noqa: E731
+        # (a job without windows has no work: the call leaves its profile alone, and it is all zeros)
+        prof = lambda f, km, nw: (f[: flank_words(km.size, flanks)] if nw else  # noqa: E731
+                                  np.zeros(flank_words(km.size, flanks), np.uint32)).reshape(2, km.size, flanks, 5)
         return [WindowHits(c[: km.size], m[: hits_words(km.size, nw, E)].reshape(E + 1, nw, (km.size + 31) // 32), km.size,
-                           shape(p, km, nw), L, self, shape(t, km, nw) if spans else None, int(k))
-                for (km, c, nw, L), m, p, t in zip(keep, mats, planes, starts)]
+                           shape(p, km, nw), L, self, shape(t, km, nw) if spans else None, int(k),
+                           prof(f, km, nw) if flanks else None)
+                for (km, c, nw, L), m, p, t, f in zip(keep, mats, planes, starts, profs)]
 
     def hit_start_positions(self, k: int, kmers, n_kmers: int, sample, window_len: int, hits, pos, levels: int,
                             out=None, stream=None):
@@ -705,6 +753,28 @@ class ApproxCounter:
                                                     p(hits), p(pos), int(levels), p(out), ctypes.c_void_p(stream or 0)),
               self._h)
         return out[: positions_words(n_kmers, ws.n_windows)].view(8, int(ws.n_windows), words)
+
+    def hit_flank_profile(self, sample, window_len: int, hit_plane, pos, start, n_kmers: int, n_windows: int, depth: int,
+                          out=None, stream=None):
+        """ac_hit_flank_profile_device: the flank pass alone over resident tensors -- `sample` an ACWindows of
+        device pointers (or a DeviceSegment) holding n_windows equal windows of window_len bases, `hit_plane`
+        one level plane of a device hit matrix (int32, n_windows x ceil(n_kmers / 32)), `pos` its position
+        matrix, `start` its start matrix or None (the left half is then zeros).  Returns an int32 device
+        tensor (2, n_kmers, depth, 5) (`out`, when given, is written instead; asynchronous)."""
+        import torch
+
+        ws = sample.as_struct() if hasattr(sample, "as_struct") else sample
+        ws = ws.sample if isinstance(ws, ACSegment) else ws
+        if int(n_windows) != int(ws.n_windows):
+            ws = ACWindows.from_buffer_copy(ws)  # (the first n_windows windows of the image)
+            ws.n_windows = int(n_windows)
+        n = flank_words(n_kmers, depth)
+        if out is None:
+            out = torch.empty(max(n, 1), dtype=torch.int32, device=pos.device if pos is not None else "cuda")
+        p = lambda t: ctypes.cast(ctypes.c_void_p(t.data_ptr() if t is not None else 0), _lib.p32)  # noqa: E731
+        check(self._L.ac_hit_flank_profile_device(self._h, ctypes.byref(ws), int(window_len), p(hit_plane), p(pos), p(start),
+                                                  int(n_kmers), int(depth), p(out), ctypes.c_void_p(stream or 0)), self._h)
+        return out[:n].view(2, int(n_kmers), int(depth), 5)
 
     def hit_position_profile(self, hits, pos, n_kmers: int, n_windows: int, levels: int, window_len: int, stream=None):
         """ac_hit_position_profile_device over a device hit matrix (`levels` planes) and its position

@@ -290,6 +290,7 @@ void ac_destroy(ac_ctx* ctx) {
     if (ctx->d_hits) (void)hipFree(ctx->d_hits);
     if (ctx->d_pos) (void)hipFree(ctx->d_pos);
     if (ctx->d_start) (void)hipFree(ctx->d_start);
+    if (ctx->d_flank) (void)hipFree(ctx->d_flank);
     if (ctx->d_cooc) (void)hipFree(ctx->d_cooc);
     if (ctx->d_cooc_io) (void)hipFree(ctx->d_cooc_io);
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
@@ -568,10 +569,15 @@ ac_status ac_count(ac_ctx* ctx, uint32_t k, const uint64_t* kmers, uint32_t n_km
 
 // ac_error_count_samples, and -- hits_host: one host matrix per job -- ac_window_hits_samples, and --
 // pos_host beside it -- ac_window_positions_samples, and -- start_host beside both: the span pass over every
-// job's device matrices after the launch -- ac_window_spans_samples.
-static ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, uint32_t n_jobs,
-                               uint32_t* const* hits_host, uint32_t* const* pos_host = nullptr,
-                               uint32_t* const* start_host = nullptr) {
+// job's device matrices after the launch -- ac_window_spans_samples, and -- flank_host beside the three: the
+// flank pass of `depth` bases over the top level plane and the two matrices after that --
+// ac_window_flanks_samples (capi_flank.cpp).
+}  // extern "C"
+
+namespace ac_detail {
+ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, uint32_t n_jobs, uint32_t* const* hits_host,
+                        uint32_t* const* pos_host, uint32_t* const* start_host, uint32_t* const* flank_host,
+                        uint32_t depth) {
     if (!ctx) return fail(nullptr, AC_ERR_INVALID, "ctx is NULL");
     if (ac_status st = check_k(ctx, k)) return st;
     if (n_jobs > AC_MAX_JOBS) return fail(ctx, AC_ERR_INVALID, "too many jobs in one call (max 4)");
@@ -612,6 +618,8 @@ static ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* job
     uint32_t* d_pos[AC_MAX_JOBS] = {};
     size_t pos_bytes[AC_MAX_JOBS] = {};
     uint32_t* d_start[AC_MAX_JOBS] = {};
+    uint32_t* d_flank[AC_MAX_JOBS] = {};
+    size_t flank_bytes[AC_MAX_JOBS] = {};
     if (hits_host) {
         bool live[AC_MAX_JOBS];
         for (uint32_t j = 0; j < n_jobs; ++j) live[j] = jobs[j].n_kmers && jobs[j].sample.n_windows;
@@ -632,7 +640,15 @@ static ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* job
                     return fail(ctx, AC_ERR_INVALID, "window positions: pos_host[j] is NULL for a job with work");
                 if (start_host && live[j] && !start_host[j])
                     return fail(ctx, AC_ERR_INVALID, "match spans: start_host[j] is NULL for a job with work");
+                if (start_host && flank_host && live[j] && !flank_host[j])
+                    return fail(ctx, AC_ERR_INVALID, "flank profile: flank_host[j] is NULL for a job with work");
                 all_pos += align256(pos_bytes[j]);
+            }
+        size_t all_flank = 0;
+        if (pos_host && start_host && flank_host)
+            for (uint32_t j = 0; j < n_jobs; ++j) {
+                flank_bytes[j] = live[j] ? sizeof(uint32_t) * (size_t)ac_hit_flank_words(jobs[j].n_kmers, depth) : 0;
+                all_flank += align256(flank_bytes[j]);
             }
         AC_HIP(ctx, hipSetDevice(ctx->device));
         if (ac_status s2 = grow(ctx, &ctx->d_hits, &ctx->d_hits_cap, all)) return s2;
@@ -640,7 +656,9 @@ static ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* job
             if (ac_status s2 = grow(ctx, &ctx->d_pos, &ctx->d_pos_cap, all_pos)) return s2;
         if (pos_host && start_host)
             if (ac_status s2 = grow(ctx, &ctx->d_start, &ctx->d_start_cap, all_pos)) return s2;
-        size_t at = 0, at_pos = 0;
+        if (all_flank)
+            if (ac_status s2 = grow(ctx, &ctx->d_flank, &ctx->d_flank_cap, all_flank)) return s2;
+        size_t at = 0, at_pos = 0, at_flank = 0;
         for (uint32_t j = 0; j < n_jobs; ++j) {
             d_hits[j] = (uint32_t*)((char*)ctx->d_hits + at);
             at += align256(hits_bytes[j]);
@@ -648,6 +666,10 @@ static ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* job
                 d_pos[j] = (uint32_t*)((char*)ctx->d_pos + at_pos);
                 if (start_host) d_start[j] = (uint32_t*)((char*)ctx->d_start + at_pos);
                 at_pos += align256(pos_bytes[j]);
+            }
+            if (all_flank) {
+                d_flank[j] = (uint32_t*)((char*)ctx->d_flank + at_flank);
+                at_flank += align256(flank_bytes[j]);
             }
         }
     }
@@ -693,6 +715,15 @@ static ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* job
                                                d_pos[j], ctx->max_errors + 1u, d_start[j], st))
                     return rc;
                 AC_HIP(ctx, hipMemcpyAsync(start_host[j], d_start[j], pos_bytes[j], hipMemcpyDeviceToHost, st));
+                if (flank_host) {
+                    // (the top level plane: plane E of the E + 1, each one ac_window_hits_words at budget 0)
+                    const uint32_t* top = d_hits[j] + (size_t)ctx->max_errors *
+                                                          (size_t)ac_window_hits_words(jobs[j].n_kmers, jobs[j].sample.n_windows, 0u);
+                    if (ac_status rc = flank_device(ctx, &jobs[j].sample, ulen[j], top, d_pos[j], d_start[j], jobs[j].n_kmers,
+                                                    depth, d_flank[j], st))
+                        return rc;
+                    AC_HIP(ctx, hipMemcpyAsync(flank_host[j], d_flank[j], flank_bytes[j], hipMemcpyDeviceToHost, st));
+                }
             }
     if (ac_status rc = ac_check(ctx, st)) return rc;  // synchronises the stream
     base = 0;
@@ -700,6 +731,9 @@ static ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* job
         for (uint32_t i = 0; i < jobs[j].n_kmers; ++i) jobs[j].counts[i] = ctx->h_counts[base++];
     return AC_OK;
 }
+}  // namespace ac_detail
+
+extern "C" {
 
 ac_status ac_error_count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, uint32_t n_jobs) {
     return count_samples(ctx, k, jobs, n_jobs, nullptr);

@@ -21,6 +21,10 @@
 //                   file: per k-mer, in the same order, for every base 1..L how many of the windows within E edits
 //                   have their best occurrence starting there, and for every occurrence length k - E .. k + E how
 //                   many have that length (ac_window_spans_samples)
+//   --flanks D      beside every <out>_<run>.<end> file a <out>_<run>.<end>.flanks file: per k-mer, in the same
+//                   order, the windows within E edits by the base (a,c,g,t,n) at each of the D bases before its
+//                   best occurrence's start and the D bases after its end, in reading order
+//                   (ac_window_flanks_samples)
 //   --cooccurrence  beside every <out>_<run>.<end> file a <out>_<run>.<end>.cooc file: per k-mer, in the same
 //                   order, for every k-mer of the file how many sampled windows hold the two together within
 //                   E edits (two of the reference's bitfields at once; ac_hit_cooccurrence)
@@ -115,6 +119,13 @@ const Opt OPTS[] = {
      "starts at that base; a .lengths line is the k-mer and the number of those windows by occurrence length, from "
      "k - max-errors to k + max-errors. Both sum to the last column of its .levels line. Same needs as --levels, with "
      "which and with --positions it can be combined."},
+    {"", "flanks", Kind::Int,
+     "[MI355X build] also write <out>_<run>.<end>.flanks, for a depth D of 1 to 32: one line per k-mer of the main "
+     "file, in its order. A line is the k-mer and 2 D groups a,c,g,t,n: of the sampled windows holding it within "
+     "max-errors edits, how many have that base at each of the D bases before its best occurrence's start (from the "
+     "farthest to the nearest) and at each of the D bases after its end (from the nearest to the farthest), so that a "
+     "line reads like the window; a base outside the window is not counted. Same needs as --levels, with which and "
+     "with --positions and --spans it can be combined."},
     {"", "cooccurrence", Kind::Flag,
      "[MI355X build] also write <out>_<run>.<end>.cooc: one line per k-mer of the main file, in its order, the "
      "k-mer and, for every k-mer of the main file in the same order, the number of sampled windows holding both "
@@ -373,6 +384,33 @@ bool export_spans(const pair_vector& ranked, const std::vector<uint64_t>& kmers,
     return std::fclose(f) == 0;
 }
 
+// --flanks: one line per k-mer of `ranked`, the k-mer and 2 D groups a,c,g,t,n -- `flank` is the result of
+// ac_window_flanks_samples (2 sides x n x D x 5, candidate c = kmers[c]): the left side's columns from the
+// farthest base to the nearest, then the right side's from the nearest to the farthest.
+bool export_flanks(const pair_vector& ranked, const std::vector<uint64_t>& kmers, const std::vector<uint32_t>& flank,
+                   uint32_t depth, uint32_t k, const std::string& path) {
+    const size_t n = kmers.size(), D = depth;
+    std::map<uint64_t, uint32_t> index;  // (the exact count's k-mers are distinct)
+    for (uint32_t c = 0; c < n; ++c) index.emplace(kmers[c], c);
+    std::FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) return false;
+    std::string line;
+    auto group = [&](size_t side, size_t c, size_t j) {
+        const uint32_t* g = flank.data() + ((side * n + c) * D + j) * 5;
+        line += '\t';
+        for (int s = 0; s < 5; ++s) line += (s ? "," : "") + std::to_string(g[s]);
+    };
+    for (const auto& kv : ranked) {
+        const uint32_t c = index.at(kv.first);
+        line = int2dna(kv.first, k);
+        for (size_t j = D; j-- > 0;) group(1, c, j);
+        for (size_t j = 0; j < D; ++j) group(0, c, j);
+        line += '\n';
+        std::fwrite(line.data(), 1, line.size(), f);
+    }
+    return std::fclose(f) == 0;
+}
+
 // --cooccurrence: one line per k-mer of `ranked`, the k-mer and one count per k-mer of `ranked` in the same
 // order -- `cooc` is the n x n result of ac_hit_cooccurrence over the job's top level plane, candidate c =
 // kmers[c], permuted here into the main file's order.
@@ -467,7 +505,7 @@ int main(int argc, char const** argv) {
     uint64_t solid_km = 0, nb_thread = 4, k = 16, sl = 100, sn = 40000, limit = 500, v = 1, nb_of_runs = 1;
     float param_lc = 1.0f, lc = 1.0f;
     bool skip_end = false;
-    uint64_t n_gpus = 1, max_errors = 2;
+    uint64_t n_gpus = 1, max_errors = 2, flank_depth = 0;
     std::string seed_str;
 
     // Config file (721-737): CLI > config > defaults
@@ -504,11 +542,13 @@ int main(int argc, char const** argv) {
     get_option(args, "gpus", n_gpus);
     get_option(args, "seed", seed_str);
     get_option(args, "max-errors", max_errors);
+    get_option(args, "flanks", flank_depth);
     skip_end = skip_end || args.val.count("skip_end");
     const bool host_exact = args.val.count("host-exact") > 0;
     const bool levels = args.val.count("levels") > 0;
     const bool positions = args.val.count("positions") > 0;
     const bool spans = args.val.count("spans") > 0;
+    const bool flanks = args.val.count("flanks") > 0;
     const bool cooccurrence = args.val.count("cooccurrence") > 0;
     const bool paired = args.val.count("paired-sample") > 0;
     const bool cross = args.val.count("cross-cooccurrence") > 0;
@@ -566,10 +606,12 @@ int main(int argc, char const** argv) {
     // library refuses when the count is asked for.
     // --positions: the same kernels' sibling family, the same constraints and messages.
     // --spans: a pass over the positions call's matrices, so the same again.
+    // --flanks: a pass over the spans call's matrices, so the same again; and its depth.
     // --cooccurrence, --cross-cooccurrence: reductions of the same hit matrices, so the same again.
     const std::pair<const char*, bool> hit_flags[] = {{"--levels", levels},
                                                       {"--positions", positions},
                                                       {"--spans", spans},
+                                                      {"--flanks", flanks},
                                                       {"--cooccurrence", cooccurrence},
                                                       {"--cross-cooccurrence", cross}};
     for (const auto& hf : hit_flags) {
@@ -584,6 +626,10 @@ int main(int argc, char const** argv) {
             std::cerr << error_pref << flag << why << std::endl;
             return 1;
         }
+    }
+    if (flanks && (flank_depth < 1 || flank_depth > 32)) {
+        std::cerr << error_pref << "--flanks needs a depth of 1 to 32" << std::endl;
+        return 1;
     }
     lc = adjust_threshold(param_lc, 16, (uint32_t)k);
 
@@ -670,6 +716,9 @@ int main(int argc, char const** argv) {
             // --spans: the spans call, which yields all of that and the start matrices
             std::vector<std::vector<uint32_t>> start(pending.size());
             std::vector<uint32_t*> start_p(pending.size());
+            // --flanks: the flanks call, which yields all of that and the flank profiles
+            std::vector<std::vector<uint32_t>> flank(pending.size());
+            std::vector<uint32_t*> flank_p(pending.size());
             // --cooccurrence: the hits call as well, then the top level plane's co-occurrence
             std::vector<std::vector<uint32_t>> cooc(pending.size());
             // --cross-cooccurrence: the hits call as well, then the two ends' top level planes against each other
@@ -680,22 +729,29 @@ int main(int argc, char const** argv) {
                 const bool on_device = !host_exact && dev.shards == 1;  // the samples uploaded for the exact count
                 for (size_t e = 0; e < pending.size(); ++e)
                     jobs[e].sample = on_device ? pending[e].dsample : view(pending[e].img);
-                if (levels || positions || spans || cooccurrence || cross)
+                if (levels || positions || spans || flanks || cooccurrence || cross)
                     for (size_t e = 0; e < pending.size(); ++e) {
                         hits[e].assign((size_t)ac_window_hits_words(jobs[e].n_kmers, jobs[e].sample.n_windows,
                                                                     (uint32_t)max_errors) + 1, 0u);
                         hits_p[e] = hits[e].data();
-                        if (positions || spans) {
+                        if (positions || spans || flanks) {
                             pos[e].assign((size_t)ac_window_positions_words(jobs[e].n_kmers, jobs[e].sample.n_windows) + 1, 0u);
                             pos_p[e] = pos[e].data();
                         }
-                        if (spans) {
+                        if (spans || flanks) {
                             start[e].assign(pos[e].size(), 0u);
                             start_p[e] = start[e].data();
                         }
+                        if (flanks) {
+                            flank[e].assign((size_t)ac_hit_flank_words(jobs[e].n_kmers, (uint32_t)flank_depth) + 1, 0u);
+                            flank_p[e] = flank[e].data();
+                        }
                     }
                 const ac_status st =
-                    spans       ? ac_window_spans_samples(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size(), hits_p.data(),
+                    flanks      ? ac_window_flanks_samples(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size(),
+                                                           (uint32_t)flank_depth, hits_p.data(), pos_p.data(), start_p.data(),
+                                                           flank_p.data())
+                    : spans     ? ac_window_spans_samples(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size(), hits_p.data(),
                                                           pos_p.data(), start_p.data())
                     : positions ? ac_window_positions_samples(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size(),
                                                               hits_p.data(), pos_p.data())
@@ -760,6 +816,12 @@ int main(int argc, char const** argv) {
                                   (uint32_t)k, path + ".starts", path + ".lengths")) {
                     std::cerr << error_pref + "Failed to export the match spans" << std::endl;
                     std::cerr << "Path: " << path + ".starts" << std::endl;
+                    return false;
+                }
+                if (flanks && !export_flanks(sorted_error_count, km[e], flank[e], (uint32_t)flank_depth, (uint32_t)k,
+                                             path + ".flanks")) {
+                    std::cerr << error_pref + "Failed to export the flank profiles" << std::endl;
+                    std::cerr << "Path: " << path + ".flanks" << std::endl;
                     return false;
                 }
                 if (cooccurrence && !export_cooccurrence(sorted_error_count, km[e], cooc[e], (uint32_t)k, path + ".cooc")) {

@@ -360,6 +360,13 @@ hipError_t launch_hit_window_counts(const uint32_t* hits, uint32_t n_kmers, uint
 hipError_t launch_hit_start_positions(uint32_t k, const uint64_t* kmers, uint32_t n_kmers, const uint32_t* codes,
                                       const uint32_t* nmask, uint32_t n_windows, uint32_t window_len, const uint32_t* hits,
                                       const uint32_t* pos, uint32_t levels, uint32_t* start, hipStream_t stream);
+// hit_flank.hip: the flank profile (hit_flank.h: 2 x n_kmers x depth x 5 words) of one level plane `hit`, its
+// position matrix and -- or NULL: the left half stays 0 -- its start matrix over equal windows of window_len
+// bases (1..256) at ceil32 strides of the image codes / nmask; depth 1..32; flank is zeroed on the stream
+// first (n_kmers = 0: no work; n_windows = 0: the zeroes alone)
+hipError_t launch_hit_flank_profile(const uint32_t* codes, const uint32_t* nmask, uint32_t n_windows, uint32_t window_len,
+                                    const uint32_t* hit, const uint32_t* pos, const uint32_t* start, uint32_t n_kmers,
+                                    uint32_t depth, uint32_t* flank, hipStream_t stream);
 
 // Waves of the count kernel for pattern pack P that fit on the device at once.
 hipError_t resident_waves(uint32_t P, bool staged, int cu_count, uint32_t* waves);

@@ -604,6 +604,67 @@ ac_status ac_window_spans_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* 
                                   uint32_t* const* hits_host, uint32_t* const* pos_host, uint32_t* const* start_host);
 
 /*
+ * Flank profiles: the bases after and before each k-mer's best occurrence
+ * (additive exports of ABI 8).  Everything above reduces the hit matrix per
+ * k-mer or per pair of k-mers; none of it reads the window's text around an
+ * occurrence.  For a k-mer inside an adapter the bases after its occurrence are
+ * the adapter's next bases in almost every read, for the adapter's last k-mer
+ * they are insert: a per-k-mer histogram of the D bases after the end and the D
+ * bases before the start extends every k-mer by majority vote and shows where
+ * the adapter ends.  With w a window of L bases (equal windows, L in 1..256, at
+ * ceil32(L)-base strides), c a k-mer, H a hit plane (n_windows x
+ * ceil(n_kmers / 32) words: one level plane of a hit matrix), pos(c, w) the
+ * exclusive end from the position matrix, start(c, w) the inclusive start from
+ * the start matrix, the symbols A, C, G, T = 0..3 and N = 4 (any base whose N
+ * bit is set) and the depth D in 1..32,
+ *     right[c][j][s] = #{ w : H(w, c), q = pos(c, w) + j       <  L, sym(w[q]) = s }
+ *     left [c][j][s] = #{ w : H(w, c), q = start(c, w) - 1 - j >= 0, sym(w[q]) = s }
+ * for j = 0..D-1, stored as u32
+ *     flank[((side * n_kmers + c) * D + j) * 5 + s]     side 0 = right, 1 = left
+ * ac_hit_flank_words(n_kmers, depth) = 2 n_kmers D 5 words in all.  A base
+ * outside [0, L) is not counted, so the sum over s of right[c][j] is the number
+ * of hit windows whose occurrence ends at or before L - j - 1; slot padding is
+ * never read as text.  Every word is defined when the stream work is done: the
+ * caller clears nothing.  Bits of candidates >= n_kmers are ignored.  The
+ * planes may hold anything: a pair whose stored position is past L or whose
+ * start is not below its end contributes to neither side, and nothing outside
+ * the windows is read.  Passing a lower plane e < E of a hit matrix selects the
+ * pairs within e edits; their positions are the ones the matrices hold.
+ *   ac_hit_flank_profile_device
+ *       the pass alone: from the device sample (codes and nmask are read, bases
+ *       below window_len only; start / length are not), one device level plane,
+ *       the position matrix and the start matrix, into flank_out (device
+ *       memory).  Asynchronous on hip_stream.  `start` may be NULL: the left
+ *       half of the result is then zeros.  Its work follows the hit pairs; the
+ *       observations of a tile of 32 k-mers over a strip of windows are summed
+ *       in on-chip memory and added to the output once.  Runs on any context,
+ *       whatever AC_BITSLICE, k and the budget are; an ac_create_multi context
+ *       uses its first device.  AC_ERR_INVALID before anything is enqueued, the
+ *       constraint in ac_last_error, for: a NULL ctx; depth outside 1..32;
+ *       window_len outside 1..256; n_windows x ceil32(window_len) past n_bases;
+ *       a NULL sample, codes or nmask; a NULL plane, pos or output when there
+ *       is work.  The context stays usable.  n_kmers = 0 is no work;
+ *       n_windows = 0 writes zeros.
+ *   ac_window_flanks_samples
+ *       ac_window_spans_samples followed, per job with work, by the pass on the
+ *       context's stream over the resident sample and the context's device
+ *       matrices at the top level E, then copied out (flank_host[j],
+ *       ac_hit_flank_words u32).  Synchronous.  Refuses exactly what
+ *       ac_window_spans_samples refuses, plus a depth outside 1..32 and a NULL
+ *       flank buffer for a job with work.
+ * Not built: flanks from the jobs stage and from word-parallel launches (as for
+ * the spans), per-distance flank planes, and flanks of another occurrence than
+ * the one the matrices hold.
+ */
+uint64_t ac_hit_flank_words(uint32_t n_kmers, uint32_t depth);
+ac_status ac_hit_flank_profile_device(ac_ctx* ctx, const ac_windows* sample, uint32_t window_len,
+                                      const uint32_t* hit_plane, const uint32_t* pos, const uint32_t* start,
+                                      uint32_t n_kmers, uint32_t depth, uint32_t* flank_out, void* hip_stream);
+ac_status ac_window_flanks_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, uint32_t n_jobs, uint32_t depth,
+                                   uint32_t* const* hits_host, uint32_t* const* pos_host,
+                                   uint32_t* const* start_host, uint32_t* const* flank_host);
+
+/*
  * Hit levels and end positions from the jobs stage (additive exports of ABI 8):
  * ac_error_count_jobs / _submit -- Dna5 windows in, the whole errorCount stage --
  * that also return the matrices above, from the same one launch: packing still

@@ -22,6 +22,9 @@ positions"); --profile then times ac_hit_position_profile_device over the first 
 every segment's matrices on resident input, in rounds interleaved with the hits-and-positions launch that produces
 its input, and prints the top level plane's hit density; --random-windows replaces every window by random bases (no
 planted occurrence: a density near 0, to see whether the pass's time follows the hits or the pairs).
+--flanks D (with --positions --spans) also times the flank pass (ac_hit_flank_profile_device, DESIGN.md 4e "Flank
+profiles") at depth D over every segment's top level plane, position matrix and start matrix, in the same interleaved
+rounds, beside the floor of reading the 17 planes once at the measured HBM rate.
 --cooc (with --hits or --positions) then times the co-occurrence of the first segment's top level plane on the
 resident matrix (ac_hit_cooccurrence_device, DESIGN.md 4e "Co-occurrence"): the transposition and the product on
 their own (ac_testing_hit_cooccurrence_stages) and the whole call, beside the level counter on the same plane and
@@ -67,6 +70,9 @@ def main():
     ap.add_argument("--spans", action="store_true",
                     help="with --positions: also time ac_hit_start_positions_device over every segment's matrices, "
                          "interleaved with the launch, and print the top plane's hit density")
+    ap.add_argument("--flanks", default="", metavar="D[,D..]",
+                    help="with --positions --spans: also time ac_hit_flank_profile_device at depth D (1..32; several: "
+                         "each in turn) over every segment's matrices, in the same interleaved rounds")
     ap.add_argument("--random-windows", action="store_true",
                     help="replace every window by random bases of the same length (no planted occurrence)")
     ap.add_argument("--cooc", action="store_true",
@@ -77,6 +83,7 @@ def main():
                          "segments' top level planes: transpositions, product and the whole call, beside the Gram call")
     a = ap.parse_args()
     a.hits = a.hits or a.positions
+    a.flanks = [int(x) for x in a.flanks.split(",") if x]
     import torch
 
     import approx_counter_amd as ac
@@ -260,10 +267,18 @@ def main():
                     c.hit_start_positions(args.k, segs[i].kmers, segs[i].n_kmers, segs[i], wlen[i], hits[i], pos[i], lv,
                                           out=starts[i])
 
-            rounds, t_launch, t_pass = 5, [], []
+            flank_out = [torch.empty(max(ac.flank_words(s.n_kmers, 32), 1), dtype=torch.int32, device="cuda") for s in segs]
+            tops = [hits[i][E * s.n_windows * ((s.n_kmers + 31) // 32):] for i, s in enumerate(segs)]
+
+            def the_flank_pass(D):
+                for i in live:
+                    c.hit_flank_profile(segs[i], wlen[i], tops[i], pos[i], starts[i], segs[i].n_kmers, segs[i].n_windows,
+                                        D, out=flank_out[i])
+
+            rounds, t_launch, t_pass, t_flank = 5, [], [], {D: [] for D in a.flanks}
             for r in range(rounds):  # a round: the launch's calls, then the pass's, on the same box minutes apart at most
                 for call, into in ((lambda: c.count_device(args.k, arr, window_len=wlen, hits=hits, positions=pos), t_launch),
-                                   (the_pass, t_pass)):
+                                   (the_pass, t_pass)) + tuple((lambda D=D: the_flank_pass(D), t_flank[D]) for D in a.flanks):
                     for i in range(a.warmup + a.launches):
                         if i == a.warmup:
                             t0.record()
@@ -300,6 +315,25 @@ def main():
                   f"(rounds: pass {', '.join(f'{x:.4f}' for x in t_pass)}; launch {', '.join(f'{x:.4f}' for x in t_launch)}); "
                   f"op model {steps} columns = {ops:.3e} lane-ops = {ops / bench.VALU_PEAK_OPS * 1e3:.5f} ms at the VALU "
                   f"peak, {ops / bench.VALU_PEAK_OPS * 1e3 / mp * 100:.2f} % of the pass's time")
+            for D in a.flanks:
+                mf, obs = sum(t_flank[D]) / rounds, 0
+                the_flank_pass(D)
+                for i in live:
+                    s = segs[i]
+                    fl = flank_out[i][: ac.flank_words(s.n_kmers, D)].view(2, s.n_kmers, D, 5).to(torch.int64)
+                    prof = c.hit_position_profile(tops[i], pos[i], s.n_kmers, s.n_windows, 1, wlen[i]).to(torch.int64)
+                    # the right side's column j sums to the windows whose occurrence ends at or before L - j - 1
+                    head = torch.cumsum(prof[0], dim=1)
+                    for jj in range(D):
+                        want = head[:, wlen[i] - jj - 2] if wlen[i] - jj - 2 >= 0 else torch.zeros_like(head[:, 0])
+                        assert bool((fl[0, :, jj].sum(dim=1) == want).all()), "a right column is not the position profile's head"
+                    obs += int(fl.sum())
+                planes_b = 17 * 4 * sum(segs[i].n_windows * ((segs[i].n_kmers + 31) // 32) for i in live)
+                floor = planes_b / 6.29e12 * 1e3  # (MI355X_MICROARCH.md: 6.29 TB/s measured of the 8.0 TB/s spec)
+                print(f"flank pass, k {args.k} E {E} D {D}: {obs} observations of {hit_pairs} pairs; pass {mf:.4f} ms "
+                      f"(rounds: {', '.join(f'{x:.4f}' for x in t_flank[D])}), launch {ml:.4f} ms, span pass {mp:.4f} ms, "
+                      f"ratio to the launch {mf / ml:.3f}; 17 planes = {planes_b} bytes, {floor:.5f} ms at 6.29 TB/s, "
+                      f"{floor / mf * 100:.2f} % of the pass's time")
         if a.positions and a.profile:
             s0 = segs[0]
             for i in range(a.warmup + a.launches):
