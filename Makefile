@@ -30,13 +30,13 @@ OBJDIR := build/obj
 endif
 
 # the C-ABI layer: host code over the HIP runtime (hipcc as a C++ compiler: no kernel in these) ...
-CAPI := capi count_launch capi_exact capi_comm capi_cooc capi_cross capi_span capi_flank
+CAPI := capi count_launch capi_exact capi_comm capi_cooc capi_cross capi_span capi_flank capi_edit
 # ... and plain host C++ (g++): the worker pool + AVX packer, the jobs stage's plan
 HOSTONLY := host_pack stage_plan
 HDRS := $(INC)/approx_counter_amd.h $(INC)/approx_counter_amd_testing.h $(CSRC)/wm_count.h $(CSRC)/exact_count.h \
 	$(CSRC)/host_pack.h $(CSRC)/nrec.h $(CSRC)/ctx.h $(CSRC)/stage_plan.h $(CSRC)/bs_nfa.h $(CSRC)/bs_nfa_r.h \
 	$(CSRC)/hit_levels.h $(CSRC)/bs_pos.h $(CSRC)/hit_cooc.h $(CSRC)/hit_cross.h $(CSRC)/hit_span.h \
-	$(CSRC)/hit_flank.h
+	$(CSRC)/hit_flank.h $(CSRC)/hit_edit.h
 INCS := -I$(INC) -I$(CSRC)
 # host-only code that includes the HIP headers (no kernel, no <<<>>>)
 HIP_HOST := -D__HIP_PLATFORM_AMD__ -I$(ROCM_PATH)/include
@@ -90,7 +90,7 @@ $(HOSTONLY:%=$(OBJDIR)/%.o): $(OBJDIR)/%.o: $(CSRC)/%.cpp $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(CXX) $(HOST_CXXFLAGS) $(HIP_HOST) $(INCS) -c $< -o $@
 
-$(LIB): $(OBJDIR)/wm_count.o $(BS_UNITS:%=$(OBJDIR)/%.o) $(OBJDIR)/hit_cooc.o $(OBJDIR)/hit_cross.o $(OBJDIR)/hit_span.o $(OBJDIR)/hit_flank.o $(OBJDIR)/exact_count.o $(OBJDIR)/jobs_stage.o $(CAPI:%=$(OBJDIR)/%.o) $(HOSTONLY:%=$(OBJDIR)/%.o)
+$(LIB): $(OBJDIR)/wm_count.o $(BS_UNITS:%=$(OBJDIR)/%.o) $(OBJDIR)/hit_cooc.o $(OBJDIR)/hit_cross.o $(OBJDIR)/hit_span.o $(OBJDIR)/hit_flank.o $(OBJDIR)/hit_edit.o $(OBJDIR)/exact_count.o $(OBJDIR)/jobs_stage.o $(CAPI:%=$(OBJDIR)/%.o) $(HOSTONLY:%=$(OBJDIR)/%.o)
 	@mkdir -p $(dir $@)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -pthread
 
@@ -98,7 +98,7 @@ $(HOSTLIB): $(HOST_SRC) $(HOSTDIR)/host_capi.cpp $(HOST_HDRS)
 	@mkdir -p $(LIBDIR)
 	$(CXX) $(HOST_CXXFLAGS) -Iinclude -I$(HOSTDIR) -shared -o $@ $(HOST_SRC) $(HOSTDIR)/host_capi.cpp
 
-$(CLI): $(HOSTDIR)/adaptfinder.cpp $(HOST_SRC) $(HOST_HDRS) $(CSRC)/hit_levels.h $(CSRC)/bs_nfa.h $(CSRC)/bs_nfa_r.h $(CSRC)/bs_pos.h $(CSRC)/hit_cooc.h $(CSRC)/hit_flank.h $(LIB)
+$(CLI): $(HOSTDIR)/adaptfinder.cpp $(HOST_SRC) $(HOST_HDRS) $(CSRC)/hit_levels.h $(CSRC)/bs_nfa.h $(CSRC)/bs_nfa_r.h $(CSRC)/bs_pos.h $(CSRC)/hit_cooc.h $(CSRC)/hit_flank.h $(CSRC)/hit_edit.h $(LIB)
 	@mkdir -p $(BINDIR)
 	$(CXX) $(HOST_CXXFLAGS) -Iinclude -I$(HOSTDIR) -o $@ $(HOSTDIR)/adaptfinder.cpp $(HOST_SRC) \
 		-L$(LIBDIR) -lapprox_counter_amd -Wl,-rpath,'$$ORIGIN/../lib' -pthread
@@ -108,7 +108,7 @@ oracle:
 
 # the device assembly of every kernel unit, into build/asm
 ASM_WM := wm_count $(BS_UNITS)
-asm: $(ASM_WM:%=build/asm/%.s) build/asm/hit_cooc.s build/asm/hit_cross.s build/asm/hit_span.s build/asm/hit_flank.s
+asm: $(ASM_WM:%=build/asm/%.s) build/asm/hit_cooc.s build/asm/hit_cross.s build/asm/hit_span.s build/asm/hit_flank.s build/asm/hit_edit.s
 
 $(ASM_WM:%=build/asm/%.s): build/asm/%.s: $(CSRC)/%.hip $(WM_SRC) $(BS_INCS) $(HDRS)
 	@mkdir -p build/asm
@@ -117,6 +117,11 @@ $(ASM_WM:%=build/asm/%.s): build/asm/%.s: $(CSRC)/%.hip $(WM_SRC) $(BS_INCS) $(H
 build/asm/%.s: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p build/asm
 	$(HIPCC) $(HIPFLAGS) $(INCS) --cuda-device-only -S $< -o $@
+
+# the stand-alone host check of hit_edit.h (tests/test_edits_cpu.py builds its own, with the sanitizers on)
+build/hit_edit_check: tools/hit_edit_check.cpp $(CSRC)/hit_edit.h $(CSRC)/hit_flank.h $(CSRC)/hit_span.h $(CSRC)/bs_pos.h
+	@mkdir -p build
+	$(CXX) $(HOST_CXXFLAGS) -I$(CSRC) -o $@ $<
 
 clean:
 	rm -rf build $(LIBDIR) $(BINDIR) oracle/_build

@@ -7,11 +7,11 @@ reference interface for that path (see counter.error_count).
 """
 from .counter import (ApproxCounter, DeviceSegment, Dna5Sample, Jobs, PackedSample, WindowHits, cooccurrence_words,
                       cross_cooccurrence_words,
-                      distances_from_hits, flank_consensus, flank_words,
+                      distances_from_hits, edit_consensus, edit_words, flank_consensus, flank_words,
                       error_count, error_levels, hits_words, pack_windows, pinned_copy, pinned_empty, positions_words,
                       to_dna5, unpack_hits, unpack_positions, unpack_starts)
 from ._lib import ApproxCounterError
 
 __all__ = ["ApproxCounter", "ApproxCounterError", "DeviceSegment", "Dna5Sample", "Jobs", "PackedSample", "WindowHits",
-           "cooccurrence_words", "cross_cooccurrence_words", "distances_from_hits", "flank_consensus", "flank_words", "error_count", "error_levels", "hits_words", "pack_windows", "pinned_copy",
+           "cooccurrence_words", "cross_cooccurrence_words", "distances_from_hits", "edit_consensus", "edit_words", "flank_consensus", "flank_words", "error_count", "error_levels", "hits_words", "pack_windows", "pinned_copy",
            "pinned_empty", "to_dna5", "unpack_hits", "positions_words", "unpack_positions", "unpack_starts"]

@@ -186,6 +186,16 @@ def load():
         L.ac_window_flanks_samples.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ACSampleJob), ctypes.c_uint32,
                                                ctypes.c_uint32, pp32, pp32, pp32, pp32]
         L.ac_window_flanks_samples.restype = ctypes.c_int
+    if hasattr(L, "ac_hit_edit_words"):  # (likewise the edit profiles)
+        pp32 = ctypes.POINTER(p32)
+        L.ac_hit_edit_words.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
+        L.ac_hit_edit_words.restype = ctypes.c_uint64
+        L.ac_hit_edit_profile_device.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32,
+                                                 ctypes.POINTER(ACWindows), ctypes.c_uint32, p32, p32, p32, p32, vp]
+        L.ac_hit_edit_profile_device.restype = ctypes.c_int
+        L.ac_window_edits_samples.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ACSampleJob), ctypes.c_uint32,
+                                              ctypes.c_uint32, pp32, pp32, pp32, pp32, pp32]
+        L.ac_window_edits_samples.restype = ctypes.c_int
     if hasattr(L, "ac_window_hits_jobs"):  # (an A/B build of an older library lacks the jobs stage's hits)
         pp32 = ctypes.POINTER(p32)
         L.ac_window_hits_jobs.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ACJob), ctypes.c_uint32, pp32]

@@ -180,6 +180,46 @@ def flank_consensus(profile, min_windows: int = 1, min_share: float = 0.5) -> li
     return out
 
 
+def edit_words(n_kmers: int, k: int) -> int:
+    """ac_hit_edit_words: the u32 words of an edit profile, n_kmers x k x 12 operations."""
+    return int(n_kmers) * int(k) * 12
+
+
+def edit_consensus(profile, kmers, k: int, min_windows: int = 1, min_share: float = 0.5) -> list:
+    """The corrected string of every k-mer from its edit profile (uint32 (n_kmers, k, 12): per base of the
+    k-mer the windows by what the best occurrence holds there -- 0 match, 1..5 substituted by A C G T N,
+    6 deleted, 7..11 followed by an inserted A C G T N).  Per k-mer n is the windows its first base was aligned
+    in (operations 0..6); below min_windows the k-mer is returned as it is.  Otherwise every base is dropped
+    where it was deleted in more than min_share of the n windows, else replaced by the A/C/G/T that
+    substituted it in more than min_share of them, else kept; and after every base, kept or dropped, the
+    A/C/G/T inserted after it in more than min_share of them is appended.  min_share in [0.5, 1): at most
+    one base can hold a majority.  Pure numpy."""
+    prof = np.asarray(profile)
+    k = int(k)
+    kmers = [int(v) for v in np.asarray(kmers).reshape(-1)]
+    if prof.ndim != 3 or prof.shape != (len(kmers), k, 12):
+        raise ValueError("edit profile must be (n_kmers, k, 12)")
+    if not 0.5 <= float(min_share) < 1.0:
+        raise ValueError("min_share must be in [0.5, 1)")
+    prof = prof.astype(np.int64)
+    out = []
+    for c, v in enumerate(kmers):
+        s = "".join("ACGT"[(v >> (2 * (k - 1 - i))) & 3] for i in range(k))
+        n = int(prof[c, 0, :7].sum()) if k else 0
+        if n < int(min_windows):
+            out.append(s)
+            continue
+        need, t = float(min_share) * n, []
+        for i in range(k):
+            sub, ins = prof[c, i, 1:5], prof[c, i, 7:11]
+            if not prof[c, i, 6] > need:
+                t.append("ACGT"[int(sub.argmax())] if sub.max() > need else s[i])
+            if ins.max() > need:
+                t.append("ACGT"[int(ins.argmax())])
+        out.append("".join(t))
+    return out
+
+
 def unpack_positions(planes, hit_E, n_kmers: int) -> np.ndarray:
     """A position matrix's values: `planes` is (8, n_windows, words) uint32, plane b holding bit b of
     pos - 1; `hit_E` is bool (n_windows, n_kmers), the pairs within the budget (level E of the hit
@@ -214,7 +254,7 @@ class WindowHits:
     window_hits(..., spans=True) the match starts as well (ac_window_spans_samples)."""
 
     def __init__(self, counts, levels, n_kmers: int, planes=None, window_len: int = 0, counter=None, starts=None,
-                 k: int = 0, flanks=None):
+                 k: int = 0, flanks=None, edits=None):
         self.counts = counts
         self.levels = np.asarray(levels, dtype=np.uint32)  # (E + 1, n_windows, words)
         self.n_kmers = int(n_kmers)
@@ -223,6 +263,7 @@ class WindowHits:
         self.window_len = int(window_len)
         self.k = int(k)
         self.flanks = None if flanks is None else np.asarray(flanks, dtype=np.uint32)  # (2, n_kmers, D, 5)
+        self.edits = None if edits is None else np.asarray(edits, dtype=np.uint32)  # (n_kmers, k, 12)
         self._counter = counter
 
     def flank_profile(self) -> np.ndarray:
@@ -232,6 +273,14 @@ class WindowHits:
         if self.flanks is None:
             raise ValueError("no flank profile: ask window_hits(..., flanks=D)")
         return self.flanks
+
+    def edit_profile(self) -> np.ndarray:
+        """uint32 (n_kmers, k, 12): per k-mer and base the windows (within E edits) by what the best occurrence
+        holds there -- 0 match, 1..5 substituted by A C G T N, 6 deleted, 7..11 followed by an inserted
+        A C G T N (ac_window_edits_samples; edit_consensus(...) gives the corrected k-mers)."""
+        if self.edits is None:
+            raise ValueError("no edit profile: ask window_hits(..., edits=True)")
+        return self.edits
 
     def start_positions(self) -> np.ndarray:
         """int16 (n_windows, n_kmers): where the best occurrence starts (0-based, inclusive: the shortest
@@ -664,7 +713,8 @@ class ApproxCounter:
         """ac_error_count_samples: [(kmers, device sample from upload_sample), ...], one fused launch."""
         return self._sample_jobs(self._L.ac_error_count_samples, k, parts)
 
-    def window_hits(self, k: int, parts, positions: bool = False, spans: bool = False, flanks: int = 0) -> list:
+    def window_hits(self, k: int, parts, positions: bool = False, spans: bool = False, flanks: int = 0,
+                    edits: bool = False) -> list:
         """ac_window_hits_samples: [(kmers, PackedSample), ...] (up to 4 parts, e.g. both read ends) are
         uploaded into the context's sample slots and counted in one fused launch that also writes every
         window's hit levels; returns one WindowHits per part.  Only where the bit-sliced kernel counts
@@ -673,11 +723,12 @@ class ApproxCounter:
         WindowHits also holds the match end positions (.end_positions(), .position_profile()).  spans (implies
         positions): ac_window_spans_samples -- and the match starts (.start_positions(), .span_lengths(),
         .length_profile(), .start_profile()).  flanks = D in 1..32 (implies spans): ac_window_flanks_samples --
-        and the flank profile of D bases (.flank_profile())."""
+        and the flank profile of D bases (.flank_profile()).  edits (implies spans; with or without flanks):
+        ac_window_edits_samples -- and the edit profile (.edit_profile())."""
         if not hasattr(self._L, "ac_window_hits_samples"):
             raise _lib.ApproxCounterError(_lib.AC_ERR_INVALID, "this build of the library has no ac_window_hits_samples")
-        if positions or spans or flanks:
-            return self._window_positions(k, parts, spans or bool(flanks), int(flanks))
+        if positions or spans or flanks or edits:
+            return self._window_positions(k, parts, spans or bool(flanks) or bool(edits), int(flanks), bool(edits))
         E = self.max_errors
         keep, arr, mats = [], [], []
         for slot, (km, smp) in enumerate(parts):
@@ -696,12 +747,12 @@ class ApproxCounter:
                            counter=self)
                 for (km, c, nw), m in zip(keep, mats)]
 
-    def _window_positions(self, k: int, parts, spans: bool = False, flanks: int = 0) -> list:
-        name = "ac_window_flanks_samples" if flanks else "ac_window_spans_samples" if spans else "ac_window_positions_samples"
+    def _window_positions(self, k: int, parts, spans: bool = False, flanks: int = 0, edits: bool = False) -> list:
+        name = "ac_window_edits_samples" if edits else "ac_window_flanks_samples" if flanks else "ac_window_spans_samples" if spans else "ac_window_positions_samples"
         if not hasattr(self._L, name):
             raise _lib.ApproxCounterError(_lib.AC_ERR_INVALID, f"this build of the library has no {name}")
         E = self.max_errors
-        keep, arr, mats, planes, starts, profs = [], [], [], [], [], []
+        keep, arr, mats, planes, starts, profs, eds = [], [], [], [], [], [], []
         for slot, (km, smp) in enumerate(parts):
             km = np.ascontiguousarray(np.asarray(km, dtype=np.uint64))
             c = np.zeros(max(km.size, 1), dtype=np.uint64)
@@ -709,13 +760,19 @@ class ApproxCounter:
             planes.append(np.full(max(positions_words(km.size, smp.n_windows), 1), 0xFFFFFFFF, dtype=np.uint32))
             starts.append(np.full(max(positions_words(km.size, smp.n_windows), 1), 0xFFFFFFFF, dtype=np.uint32))
             profs.append(np.full(max(flank_words(km.size, flanks), 1), 0xFFFFFFFF, dtype=np.uint32))
+            eds.append(np.full(max(edit_words(km.size, k), 1) if edits else 1, 0xFFFFFFFF, dtype=np.uint32))
             keep.append((km, c, smp.n_windows, int(smp.length[0]) if smp.n_windows else 0))
             arr.append(ACSampleJob(_ptr(km if km.size else np.zeros(1, np.uint64), ctypes.c_uint64), int(km.size),
                                    self.upload_sample(smp, slot), _ptr(c, ctypes.c_uint64)))
         a = (ACSampleJob * len(arr))(*arr)
         hp = (_lib.p32 * len(arr))(*[_ptr(m, ctypes.c_uint32) for m in mats])
         pp = (_lib.p32 * len(arr))(*[_ptr(m, ctypes.c_uint32) for m in planes])
-        if flanks:
+        if edits:
+            sp = (_lib.p32 * len(arr))(*[_ptr(m, ctypes.c_uint32) for m in starts])
+            fp = (_lib.p32 * len(arr))(*[_ptr(m, ctypes.c_uint32) for m in profs]) if flanks else None
+            ep = (_lib.p32 * len(arr))(*[_ptr(m, ctypes.c_uint32) for m in eds])
+            check(self._L.ac_window_edits_samples(self._h, int(k), a, len(arr), int(flanks), hp, pp, sp, fp, ep), self._h)
+        elif flanks:
             sp = (_lib.p32 * len(arr))(*[_ptr(m, ctypes.c_uint32) for m in starts])
             fp = (_lib.p32 * len(arr))(*[_ptr(m, ctypes.c_uint32) for m in profs])
             check(self._L.ac_window_flanks_samples(self._h, int(k), a, len(arr), int(flanks), hp, pp, sp, fp), self._h)
@@ -728,10 +785,12 @@ class ApproxCounter:
         # (a job without windows has no work: the call leaves its profile alone, and it is all zeros)
         prof = lambda f, km, nw: (f[: flank_words(km.size, flanks)] if nw else  # noqa: E731
                                   np.zeros(flank_words(km.size, flanks), np.uint32)).reshape(2, km.size, flanks, 5)
+        edit = lambda e, km, nw: (e[: edit_words(km.size, k)] if nw else  # noqa: E731
+                                  np.zeros(edit_words(km.size, k), np.uint32)).reshape(km.size, int(k), 12)
         return [WindowHits(c[: km.size], m[: hits_words(km.size, nw, E)].reshape(E + 1, nw, (km.size + 31) // 32), km.size,
                            shape(p, km, nw), L, self, shape(t, km, nw) if spans else None, int(k),
-                           prof(f, km, nw) if flanks else None)
-                for (km, c, nw, L), m, p, t, f in zip(keep, mats, planes, starts, profs)]
+                           prof(f, km, nw) if flanks else None, edit(e, km, nw) if edits else None)
+                for (km, c, nw, L), m, p, t, f, e in zip(keep, mats, planes, starts, profs, eds)]
 
     def hit_start_positions(self, k: int, kmers, n_kmers: int, sample, window_len: int, hits, pos, levels: int,
                             out=None, stream=None):
@@ -775,6 +834,31 @@ class ApproxCounter:
         check(self._L.ac_hit_flank_profile_device(self._h, ctypes.byref(ws), int(window_len), p(hit_plane), p(pos), p(start),
                                                   int(n_kmers), int(depth), p(out), ctypes.c_void_p(stream or 0)), self._h)
         return out[:n].view(2, int(n_kmers), int(depth), 5)
+
+    def hit_edit_profile(self, k: int, kmers, n_kmers: int, sample, window_len: int, hit_plane, pos, start, n_windows: int,
+                         out=None, stream=None):
+        """ac_hit_edit_profile_device: the edit pass alone over resident tensors -- `kmers` a device pointer to
+        n_kmers k-mers (an int: a DeviceSegment's .kmers; or an int64 device tensor), `sample` an ACWindows of
+        device pointers (or a DeviceSegment) holding n_windows equal windows of window_len bases, `hit_plane`
+        one level plane of a device hit matrix (int32, n_windows x ceil(n_kmers / 32)), `pos` its position
+        matrix, `start` its start matrix.  Returns an int32 device tensor (n_kmers, k, 12) (`out`, when given,
+        is written instead; asynchronous)."""
+        import torch
+
+        ws = sample.as_struct() if hasattr(sample, "as_struct") else sample
+        ws = ws.sample if isinstance(ws, ACSegment) else ws
+        if int(n_windows) != int(ws.n_windows):
+            ws = ACWindows.from_buffer_copy(ws)  # (the first n_windows windows of the image)
+            ws.n_windows = int(n_windows)
+        n = edit_words(n_kmers, k)
+        if out is None:
+            out = torch.empty(max(n, 1), dtype=torch.int32, device=pos.device if pos is not None else "cuda")
+        p = lambda t: ctypes.cast(ctypes.c_void_p(t.data_ptr() if t is not None else 0), _lib.p32)  # noqa: E731
+        kp = kmers.data_ptr() if hasattr(kmers, "data_ptr") else (kmers or 0)
+        check(self._L.ac_hit_edit_profile_device(self._h, int(k), ctypes.cast(ctypes.c_void_p(kp), ctypes.POINTER(ctypes.c_uint64)),
+                                                 int(n_kmers), ctypes.byref(ws), int(window_len), p(hit_plane), p(pos), p(start),
+                                                 p(out), ctypes.c_void_p(stream or 0)), self._h)
+        return out[:n].view(int(n_kmers), int(k), 12)
 
     def hit_position_profile(self, hits, pos, n_kmers: int, n_windows: int, levels: int, window_len: int, stream=None):
         """ac_hit_position_profile_device over a device hit matrix (`levels` planes) and its position

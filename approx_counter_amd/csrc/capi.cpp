@@ -291,6 +291,7 @@ void ac_destroy(ac_ctx* ctx) {
     if (ctx->d_pos) (void)hipFree(ctx->d_pos);
     if (ctx->d_start) (void)hipFree(ctx->d_start);
     if (ctx->d_flank) (void)hipFree(ctx->d_flank);
+    if (ctx->d_edit) (void)hipFree(ctx->d_edit);
     if (ctx->d_cooc) (void)hipFree(ctx->d_cooc);
     if (ctx->d_cooc_io) (void)hipFree(ctx->d_cooc_io);
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
@@ -571,13 +572,14 @@ ac_status ac_count(ac_ctx* ctx, uint32_t k, const uint64_t* kmers, uint32_t n_km
 // pos_host beside it -- ac_window_positions_samples, and -- start_host beside both: the span pass over every
 // job's device matrices after the launch -- ac_window_spans_samples, and -- flank_host beside the three: the
 // flank pass of `depth` bases over the top level plane and the two matrices after that --
-// ac_window_flanks_samples (capi_flank.cpp).
+// ac_window_flanks_samples (capi_flank.cpp), and -- edit_host beside the first three, with or without
+// flank_host: the edit pass over the same plane and matrices -- ac_window_edits_samples (capi_edit.cpp).
 }  // extern "C"
 
 namespace ac_detail {
 ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, uint32_t n_jobs, uint32_t* const* hits_host,
                         uint32_t* const* pos_host, uint32_t* const* start_host, uint32_t* const* flank_host,
-                        uint32_t depth) {
+                        uint32_t depth, uint32_t* const* edit_host) {
     if (!ctx) return fail(nullptr, AC_ERR_INVALID, "ctx is NULL");
     if (ac_status st = check_k(ctx, k)) return st;
     if (n_jobs > AC_MAX_JOBS) return fail(ctx, AC_ERR_INVALID, "too many jobs in one call (max 4)");
@@ -620,6 +622,8 @@ ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, uint
     uint32_t* d_start[AC_MAX_JOBS] = {};
     uint32_t* d_flank[AC_MAX_JOBS] = {};
     size_t flank_bytes[AC_MAX_JOBS] = {};
+    uint32_t* d_edit[AC_MAX_JOBS] = {};
+    size_t edit_bytes[AC_MAX_JOBS] = {};
     if (hits_host) {
         bool live[AC_MAX_JOBS];
         for (uint32_t j = 0; j < n_jobs; ++j) live[j] = jobs[j].n_kmers && jobs[j].sample.n_windows;
@@ -642,6 +646,8 @@ ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, uint
                     return fail(ctx, AC_ERR_INVALID, "match spans: start_host[j] is NULL for a job with work");
                 if (start_host && flank_host && live[j] && !flank_host[j])
                     return fail(ctx, AC_ERR_INVALID, "flank profile: flank_host[j] is NULL for a job with work");
+                if (start_host && edit_host && live[j] && !edit_host[j])
+                    return fail(ctx, AC_ERR_INVALID, "edit profile: edit_host[j] is NULL for a job with work");
                 all_pos += align256(pos_bytes[j]);
             }
         size_t all_flank = 0;
@@ -649,6 +655,12 @@ ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, uint
             for (uint32_t j = 0; j < n_jobs; ++j) {
                 flank_bytes[j] = live[j] ? sizeof(uint32_t) * (size_t)ac_hit_flank_words(jobs[j].n_kmers, depth) : 0;
                 all_flank += align256(flank_bytes[j]);
+            }
+        size_t all_edit = 0;
+        if (pos_host && start_host && edit_host)
+            for (uint32_t j = 0; j < n_jobs; ++j) {
+                edit_bytes[j] = live[j] ? sizeof(uint32_t) * (size_t)ac_hit_edit_words(jobs[j].n_kmers, k) : 0;
+                all_edit += align256(edit_bytes[j]);
             }
         AC_HIP(ctx, hipSetDevice(ctx->device));
         if (ac_status s2 = grow(ctx, &ctx->d_hits, &ctx->d_hits_cap, all)) return s2;
@@ -658,7 +670,9 @@ ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, uint
             if (ac_status s2 = grow(ctx, &ctx->d_start, &ctx->d_start_cap, all_pos)) return s2;
         if (all_flank)
             if (ac_status s2 = grow(ctx, &ctx->d_flank, &ctx->d_flank_cap, all_flank)) return s2;
-        size_t at = 0, at_pos = 0, at_flank = 0;
+        if (all_edit)
+            if (ac_status s2 = grow(ctx, &ctx->d_edit, &ctx->d_edit_cap, all_edit)) return s2;
+        size_t at = 0, at_pos = 0, at_flank = 0, at_edit = 0;
         for (uint32_t j = 0; j < n_jobs; ++j) {
             d_hits[j] = (uint32_t*)((char*)ctx->d_hits + at);
             at += align256(hits_bytes[j]);
@@ -670,6 +684,10 @@ ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, uint
             if (all_flank) {
                 d_flank[j] = (uint32_t*)((char*)ctx->d_flank + at_flank);
                 at_flank += align256(flank_bytes[j]);
+            }
+            if (all_edit) {
+                d_edit[j] = (uint32_t*)((char*)ctx->d_edit + at_edit);
+                at_edit += align256(edit_bytes[j]);
             }
         }
     }
@@ -715,14 +733,20 @@ ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, uint
                                                d_pos[j], ctx->max_errors + 1u, d_start[j], st))
                     return rc;
                 AC_HIP(ctx, hipMemcpyAsync(start_host[j], d_start[j], pos_bytes[j], hipMemcpyDeviceToHost, st));
+                // (the top level plane: plane E of the E + 1, each one ac_window_hits_words at budget 0)
+                const uint32_t* top = d_hits[j] + (size_t)ctx->max_errors *
+                                                      (size_t)ac_window_hits_words(jobs[j].n_kmers, jobs[j].sample.n_windows, 0u);
                 if (flank_host) {
-                    // (the top level plane: plane E of the E + 1, each one ac_window_hits_words at budget 0)
-                    const uint32_t* top = d_hits[j] + (size_t)ctx->max_errors *
-                                                          (size_t)ac_window_hits_words(jobs[j].n_kmers, jobs[j].sample.n_windows, 0u);
                     if (ac_status rc = flank_device(ctx, &jobs[j].sample, ulen[j], top, d_pos[j], d_start[j], jobs[j].n_kmers,
                                                     depth, d_flank[j], st))
                         return rc;
                     AC_HIP(ctx, hipMemcpyAsync(flank_host[j], d_flank[j], flank_bytes[j], hipMemcpyDeviceToHost, st));
+                }
+                if (edit_host) {
+                    if (ac_status rc = edit_device(ctx, k, seg[j].kmers, jobs[j].n_kmers, &jobs[j].sample, ulen[j], top, d_pos[j],
+                                                   d_start[j], d_edit[j], st))
+                        return rc;
+                    AC_HIP(ctx, hipMemcpyAsync(edit_host[j], d_edit[j], edit_bytes[j], hipMemcpyDeviceToHost, st));
                 }
             }
     if (ac_status rc = ac_check(ctx, st)) return rc;  // synchronises the stream

@@ -1,5 +1,5 @@
 // ctx.h -- the context and the helpers shared by the C-ABI translation units (capi.cpp,
-// count_launch.cpp, capi_exact.cpp, capi_comm.cpp, capi_cooc.cpp, capi_cross.cpp, capi_span.cpp, capi_flank.cpp, jobs_stage.cpp).  Private to the library:
+// count_launch.cpp, capi_exact.cpp, capi_comm.cpp, capi_cooc.cpp, capi_cross.cpp, capi_span.cpp, capi_flank.cpp, capi_edit.cpp, jobs_stage.cpp).  Private to the library:
 // nothing declared here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -41,6 +41,9 @@ struct ac_ctx {
     // ac_window_flanks_samples: the jobs' device flank profiles, likewise
     void* d_flank = nullptr;
     size_t d_flank_cap = 0;
+    // ac_window_edits_samples: the jobs' device edit profiles, likewise
+    void* d_edit = nullptr;
+    size_t d_edit_cap = 0;
     // ac_hit_cooccurrence*: the transposed planes the product reads (grow-only; stream-ordered like the
     // count scratch), and the host-buffer call's device matrix and result, back to back
     void* d_cooc = nullptr;
@@ -242,15 +245,21 @@ ac_status span_device(ac_ctx* ctx, uint32_t k, const uint64_t* kmers, uint32_t n
                       hipStream_t stream);
 
 // --- capi.cpp: the samples entry points' one body -- the count, and per job the host matrices asked for
-// (hits; hits and positions; those and starts; those and the flank profile of `depth` bases)
+// (hits; hits and positions; those and starts; those and the flank profile of `depth` bases; the first three
+// and the edit profile, with or without the flank profile)
 ac_status count_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, uint32_t n_jobs, uint32_t* const* hits_host,
                         uint32_t* const* pos_host = nullptr, uint32_t* const* start_host = nullptr,
-                        uint32_t* const* flank_host = nullptr, uint32_t depth = 0);
+                        uint32_t* const* flank_host = nullptr, uint32_t depth = 0, uint32_t* const* edit_host = nullptr);
 
 // --- capi_flank.cpp: ac_hit_flank_profile_device's checks and launch (the samples route ends here too)
 ac_status flank_device(ac_ctx* ctx, const ac_windows* sample, uint32_t window_len, const uint32_t* hit_plane,
                        const uint32_t* pos, const uint32_t* start, uint32_t n_kmers, uint32_t depth, uint32_t* flank_out,
                        hipStream_t stream);
+
+// --- capi_edit.cpp: ac_hit_edit_profile_device's checks and launch (the samples route ends here too)
+ac_status edit_device(ac_ctx* ctx, uint32_t k, const uint64_t* kmers, uint32_t n_kmers, const ac_windows* sample,
+                      uint32_t window_len, const uint32_t* hit_plane, const uint32_t* pos, const uint32_t* start,
+                      uint32_t* edit_out, hipStream_t stream);
 
 // --- capi_comm.cpp
 void comm_destroy(ac_ctx* ctx);  // the context's communicator, if it has one (ac_destroy)

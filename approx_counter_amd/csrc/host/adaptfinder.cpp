@@ -25,6 +25,10 @@
 //                   order, the windows within E edits by the base (a,c,g,t,n) at each of the D bases before its
 //                   best occurrence's start and the D bases after its end, in reading order
 //                   (ac_window_flanks_samples)
+//   --edits         beside every <out>_<run>.<end> file a <out>_<run>.<end>.edits file: per k-mer, in the same
+//                   order, for every base of the k-mer the windows within E edits by what its best occurrence
+//                   holds there: the base, another base, nothing, or an inserted base after it
+//                   (ac_window_edits_samples)
 //   --cooccurrence  beside every <out>_<run>.<end> file a <out>_<run>.<end>.cooc file: per k-mer, in the same
 //                   order, for every k-mer of the file how many sampled windows hold the two together within
 //                   E edits (two of the reference's bitfields at once; ac_hit_cooccurrence)
@@ -126,6 +130,12 @@ const Opt OPTS[] = {
      "farthest to the nearest) and at each of the D bases after its end (from the nearest to the farthest), so that a "
      "line reads like the window; a base outside the window is not counted. Same needs as --levels, with which and "
      "with --positions and --spans it can be combined."},
+    {"", "edits", Kind::Flag,
+     "[MI355X build] also write <out>_<run>.<end>.edits: one line per k-mer of the main file, in its order. A line is "
+     "the k-mer and one group of 12 counts per base of it: of the sampled windows holding it within max-errors edits, "
+     "how many have that base matched, substituted by a,c,g,t,n, deleted (missing from the read), and followed by an "
+     "inserted a,c,g,t,n in the alignment of the k-mer against its best occurrence. Same needs as --levels, with "
+     "which and with --positions, --spans and --flanks it can be combined."},
     {"", "cooccurrence", Kind::Flag,
      "[MI355X build] also write <out>_<run>.<end>.cooc: one line per k-mer of the main file, in its order, the "
      "k-mer and, for every k-mer of the main file in the same order, the number of sampled windows holding both "
@@ -411,6 +421,31 @@ bool export_flanks(const pair_vector& ranked, const std::vector<uint64_t>& kmers
     return std::fclose(f) == 0;
 }
 
+// --edits: one line per k-mer of `ranked`, the k-mer and k groups of 12 counts -- `edit` is the result of
+// ac_window_edits_samples (n x k x 12, candidate c = kmers[c]): match, substituted by a,c,g,t,n, deleted,
+// inserted after: a,c,g,t,n.
+bool export_edits(const pair_vector& ranked, const std::vector<uint64_t>& kmers, const std::vector<uint32_t>& edit, uint32_t k,
+                  const std::string& path) {
+    const size_t n = kmers.size();
+    std::map<uint64_t, uint32_t> index;  // (the exact count's k-mers are distinct)
+    for (uint32_t c = 0; c < n; ++c) index.emplace(kmers[c], c);
+    std::FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) return false;
+    std::string line;
+    for (const auto& kv : ranked) {
+        const uint32_t c = index.at(kv.first);
+        line = int2dna(kv.first, k);
+        for (size_t i = 0; i < k; ++i) {
+            const uint32_t* g = edit.data() + ((size_t)c * k + i) * 12;
+            line += '\t';
+            for (int op = 0; op < 12; ++op) line += (op ? "," : "") + std::to_string(g[op]);
+        }
+        line += '\n';
+        std::fwrite(line.data(), 1, line.size(), f);
+    }
+    return std::fclose(f) == 0;
+}
+
 // --cooccurrence: one line per k-mer of `ranked`, the k-mer and one count per k-mer of `ranked` in the same
 // order -- `cooc` is the n x n result of ac_hit_cooccurrence over the job's top level plane, candidate c =
 // kmers[c], permuted here into the main file's order.
@@ -549,6 +584,7 @@ int main(int argc, char const** argv) {
     const bool positions = args.val.count("positions") > 0;
     const bool spans = args.val.count("spans") > 0;
     const bool flanks = args.val.count("flanks") > 0;
+    const bool edits = args.val.count("edits") > 0;
     const bool cooccurrence = args.val.count("cooccurrence") > 0;
     const bool paired = args.val.count("paired-sample") > 0;
     const bool cross = args.val.count("cross-cooccurrence") > 0;
@@ -607,11 +643,13 @@ int main(int argc, char const** argv) {
     // --positions: the same kernels' sibling family, the same constraints and messages.
     // --spans: a pass over the positions call's matrices, so the same again.
     // --flanks: a pass over the spans call's matrices, so the same again; and its depth.
+    // --edits: another pass over the spans call's matrices, so the same again.
     // --cooccurrence, --cross-cooccurrence: reductions of the same hit matrices, so the same again.
     const std::pair<const char*, bool> hit_flags[] = {{"--levels", levels},
                                                       {"--positions", positions},
                                                       {"--spans", spans},
                                                       {"--flanks", flanks},
+                                                      {"--edits", edits},
                                                       {"--cooccurrence", cooccurrence},
                                                       {"--cross-cooccurrence", cross}};
     for (const auto& hf : hit_flags) {
@@ -719,6 +757,10 @@ int main(int argc, char const** argv) {
             // --flanks: the flanks call, which yields all of that and the flank profiles
             std::vector<std::vector<uint32_t>> flank(pending.size());
             std::vector<uint32_t*> flank_p(pending.size());
+            // --edits: the edits call, which yields all of that (the flank profiles when --flanks is given too) and
+            // the edit profiles
+            std::vector<std::vector<uint32_t>> edit(pending.size());
+            std::vector<uint32_t*> edit_p(pending.size());
             // --cooccurrence: the hits call as well, then the top level plane's co-occurrence
             std::vector<std::vector<uint32_t>> cooc(pending.size());
             // --cross-cooccurrence: the hits call as well, then the two ends' top level planes against each other
@@ -729,16 +771,16 @@ int main(int argc, char const** argv) {
                 const bool on_device = !host_exact && dev.shards == 1;  // the samples uploaded for the exact count
                 for (size_t e = 0; e < pending.size(); ++e)
                     jobs[e].sample = on_device ? pending[e].dsample : view(pending[e].img);
-                if (levels || positions || spans || flanks || cooccurrence || cross)
+                if (levels || positions || spans || flanks || edits || cooccurrence || cross)
                     for (size_t e = 0; e < pending.size(); ++e) {
                         hits[e].assign((size_t)ac_window_hits_words(jobs[e].n_kmers, jobs[e].sample.n_windows,
                                                                     (uint32_t)max_errors) + 1, 0u);
                         hits_p[e] = hits[e].data();
-                        if (positions || spans || flanks) {
+                        if (positions || spans || flanks || edits) {
                             pos[e].assign((size_t)ac_window_positions_words(jobs[e].n_kmers, jobs[e].sample.n_windows) + 1, 0u);
                             pos_p[e] = pos[e].data();
                         }
-                        if (spans || flanks) {
+                        if (spans || flanks || edits) {
                             start[e].assign(pos[e].size(), 0u);
                             start_p[e] = start[e].data();
                         }
@@ -746,9 +788,16 @@ int main(int argc, char const** argv) {
                             flank[e].assign((size_t)ac_hit_flank_words(jobs[e].n_kmers, (uint32_t)flank_depth) + 1, 0u);
                             flank_p[e] = flank[e].data();
                         }
+                        if (edits) {
+                            edit[e].assign((size_t)ac_hit_edit_words(jobs[e].n_kmers, (uint32_t)k) + 1, 0u);
+                            edit_p[e] = edit[e].data();
+                        }
                     }
                 const ac_status st =
-                    flanks      ? ac_window_flanks_samples(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size(),
+                    edits       ? ac_window_edits_samples(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size(),
+                                                          flanks ? (uint32_t)flank_depth : 0u, hits_p.data(), pos_p.data(),
+                                                          start_p.data(), flanks ? flank_p.data() : nullptr, edit_p.data())
+                    : flanks    ? ac_window_flanks_samples(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size(),
                                                            (uint32_t)flank_depth, hits_p.data(), pos_p.data(), start_p.data(),
                                                            flank_p.data())
                     : spans     ? ac_window_spans_samples(dev.ctx, (uint32_t)k, jobs.data(), (uint32_t)jobs.size(), hits_p.data(),
@@ -822,6 +871,11 @@ int main(int argc, char const** argv) {
                                              path + ".flanks")) {
                     std::cerr << error_pref + "Failed to export the flank profiles" << std::endl;
                     std::cerr << "Path: " << path + ".flanks" << std::endl;
+                    return false;
+                }
+                if (edits && !export_edits(sorted_error_count, km[e], edit[e], (uint32_t)k, path + ".edits")) {
+                    std::cerr << error_pref + "Failed to export the edit profiles" << std::endl;
+                    std::cerr << "Path: " << path + ".edits" << std::endl;
                     return false;
                 }
                 if (cooccurrence && !export_cooccurrence(sorted_error_count, km[e], cooc[e], (uint32_t)k, path + ".cooc")) {

@@ -367,6 +367,13 @@ hipError_t launch_hit_start_positions(uint32_t k, const uint64_t* kmers, uint32_
 hipError_t launch_hit_flank_profile(const uint32_t* codes, const uint32_t* nmask, uint32_t n_windows, uint32_t window_len,
                                     const uint32_t* hit, const uint32_t* pos, const uint32_t* start, uint32_t n_kmers,
                                     uint32_t depth, uint32_t* flank, hipStream_t stream);
+// hit_edit.hip: the edit profile (hit_edit.h: n_kmers x k x 12 words) of one level plane `hit`, its position
+// matrix and its start matrix over equal windows of window_len bases (1..256) at ceil32 strides of the image
+// codes / nmask; k 2..32, kmers on the device; edit is zeroed on the stream first (n_kmers = 0: no work;
+// n_windows = 0: the zeroes alone)
+hipError_t launch_hit_edit_profile(uint32_t k, const uint64_t* kmers, uint32_t n_kmers, const uint32_t* codes,
+                                   const uint32_t* nmask, uint32_t n_windows, uint32_t window_len, const uint32_t* hit,
+                                   const uint32_t* pos, const uint32_t* start, uint32_t* edit, hipStream_t stream);
 
 // Waves of the count kernel for pattern pack P that fit on the device at once.
 hipError_t resident_waves(uint32_t P, bool staged, int cu_count, uint32_t* waves);

@@ -665,6 +665,84 @@ ac_status ac_window_flanks_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job*
                                    uint32_t* const* start_host, uint32_t* const* flank_host);
 
 /*
+ * Edit profiles: how each k-mer's best occurrence differs from it, base by base
+ * (additive exports of ABI 8).  The calls above say whether, where and beside
+ * what a k-mer occurs; none looks inside the occurrence.  A true adapter k-mer
+ * collects edits spread thinly over its bases; an erroneous variant of one
+ * collects the same edit at the same base in most of its windows, and the
+ * profile gives its corrected string (with the flanks: prefix, corrected k-mer,
+ * extension).  With w a window of L bases (equal windows, L in 1..256, at
+ * ceil32(L)-base strides), c a k-mer of k bases (k in 2..32), H a hit plane
+ * (n_windows x ceil(n_kmers / 32) words: one level plane of a hit matrix),
+ * p = pos(c, w) the exclusive end from the position matrix, s = start(c, w) the
+ * inclusive start from the start matrix, t = w[s, p), m = p - s, an N of the
+ * window matching nothing, and D[i][j] the plain global edit-distance table of
+ * c[0, i) against t[0, j) (D[i][0] = i, D[0][j] = j): a pair counts only if
+ * H(w, c), 1 <= p <= L, s < p, |m - k| <= 3 and D[k][m] <= 3 -- 3 is the largest
+ * edit budget of this ABI and a constant of the pass, which takes no `levels`.
+ * The pair's alignment is the canonical traceback from (k, m) to (0, 0); at
+ * cell (i, j) the first rule that applies:
+ *   1. diagonal   if i > 0, j > 0 and D[i-1][j-1] + (c[i-1] != t[j-1]) = D[i][j]:
+ *                 k-mer base i-1 is matched if the bases are equal, otherwise
+ *                 substituted by t[j-1] (A, C, G, T or N); i--, j--
+ *   2. deletion   if i > 0 and D[i-1][j] + 1 = D[i][j]: k-mer base i-1 is
+ *                 deleted, that is missing from the read; i--
+ *   3. insertion  otherwise: t[j-1] is inserted after k-mer base i-1 (at i = 0
+ *                 nothing is counted); j--
+ * stored as u32
+ *     edit[(c * k + i) * 12 + op]      op 0       match
+ *                                         1..5    substituted by A C G T N
+ *                                         6       deleted
+ *                                         7..11   inserted after: A C G T N
+ * ac_hit_edit_words(n_kmers, k) = n_kmers k 12 words in all.  The cell
+ * "substituted by the k-mer's own base" stays 0.  For matrices that come from
+ * a count launch and the span pass no pair is skipped, D[k][m] is the pair's
+ * distance, no alignment begins or ends with an insertion, op 0..6 of every
+ * base sum to the plane's level count of the k-mer, and op 1..11 of a k-mer sum
+ * to the sum of its hit windows' distances.  Every word is defined when the
+ * stream work is done: the caller clears nothing.  Bits of candidates >=
+ * n_kmers are ignored.  The planes may hold anything: a pair that fails a
+ * condition counts nowhere, and nothing outside [0, L) of a window is read.
+ * Passing a lower plane e < E of a hit matrix selects the pairs within e edits.
+ *   ac_hit_edit_profile_device
+ *       the pass alone: from the k-mers (device memory, 2 bits a base, the
+ *       first base highest), the device sample (codes and nmask are read, bases
+ *       below window_len only), one device level plane, the position matrix and
+ *       the start matrix, into edit_out (device memory).  Asynchronous on
+ *       hip_stream.  Its work follows the hit pairs: a banded alignment (3
+ *       diagonals on either side) with a traceback per pair; the observations
+ *       of 32 k-mers over a strip of windows are summed in on-chip memory and
+ *       added to the output once.  Runs on any context, whatever AC_BITSLICE
+ *       and the budget are; an ac_create_multi context uses its first device.
+ *       AC_ERR_INVALID before anything is enqueued, the constraint in
+ *       ac_last_error, for: a NULL ctx; k outside 2..32; window_len outside
+ *       1..256; n_windows x ceil32(window_len) past n_bases; a NULL sample,
+ *       codes or nmask; a NULL kmers, plane, pos, start or output when there is
+ *       work.  The context stays usable.  n_kmers = 0 is no work; n_windows = 0
+ *       writes zeros.
+ *   ac_window_edits_samples
+ *       ac_window_spans_samples followed, per job with work, by the flank pass
+ *       when flank_depth is 1..32 (0, with flank_host NULL or not: no flank
+ *       pass) and by the edit pass on the context's stream over the resident
+ *       sample and the context's device matrices at the top level E, then
+ *       copied out (edit_host[j], ac_hit_edit_words u32).  Synchronous.
+ *       Refuses what ac_window_flanks_samples refuses, except that a depth of 0
+ *       is allowed, plus a NULL edit buffer for a job with work.
+ * Not built: edit profiles from the jobs stage and from word-parallel launches
+ * (as for the spans), per-distance planes (a lower plane can be passed), the
+ * alignment of another occurrence than the one the matrices hold, and
+ * assembling the corrected k-mers and flanks into adapters.
+ */
+uint64_t ac_hit_edit_words(uint32_t n_kmers, uint32_t k);
+ac_status ac_hit_edit_profile_device(ac_ctx* ctx, uint32_t k, const uint64_t* kmers, uint32_t n_kmers,
+                                     const ac_windows* sample, uint32_t window_len, const uint32_t* hit_plane,
+                                     const uint32_t* pos, const uint32_t* start, uint32_t* edit_out, void* hip_stream);
+ac_status ac_window_edits_samples(ac_ctx* ctx, uint32_t k, const ac_sample_job* jobs, uint32_t n_jobs,
+                                  uint32_t flank_depth, uint32_t* const* hits_host, uint32_t* const* pos_host,
+                                  uint32_t* const* start_host, uint32_t* const* flank_host,
+                                  uint32_t* const* edit_host);
+
+/*
  * Hit levels and end positions from the jobs stage (additive exports of ABI 8):
  * ac_error_count_jobs / _submit -- Dna5 windows in, the whole errorCount stage --
  * that also return the matrices above, from the same one launch: packing still

@@ -25,6 +25,8 @@ planted occurrence: a density near 0, to see whether the pass's time follows the
 --flanks D (with --positions --spans) also times the flank pass (ac_hit_flank_profile_device, DESIGN.md 4e "Flank
 profiles") at depth D over every segment's top level plane, position matrix and start matrix, in the same interleaved
 rounds, beside the floor of reading the 17 planes once at the measured HBM rate.
+--edits (with --positions --spans) also times the edit pass (ac_hit_edit_profile_device, DESIGN.md 4e "Edit
+profiles") over the same plane and matrices, in the same interleaved rounds, and prints its observations.
 --cooc (with --hits or --positions) then times the co-occurrence of the first segment's top level plane on the
 resident matrix (ac_hit_cooccurrence_device, DESIGN.md 4e "Co-occurrence"): the transposition and the product on
 their own (ac_testing_hit_cooccurrence_stages) and the whole call, beside the level counter on the same plane and
@@ -73,6 +75,9 @@ def main():
     ap.add_argument("--flanks", default="", metavar="D[,D..]",
                     help="with --positions --spans: also time ac_hit_flank_profile_device at depth D (1..32; several: "
                          "each in turn) over every segment's matrices, in the same interleaved rounds")
+    ap.add_argument("--edits", action="store_true",
+                    help="with --positions --spans: also time ac_hit_edit_profile_device over every segment's matrices, in "
+                         "the same interleaved rounds")
     ap.add_argument("--random-windows", action="store_true",
                     help="replace every window by random bases of the same length (no planted occurrence)")
     ap.add_argument("--cooc", action="store_true",
@@ -275,10 +280,19 @@ def main():
                     c.hit_flank_profile(segs[i], wlen[i], tops[i], pos[i], starts[i], segs[i].n_kmers, segs[i].n_windows,
                                         D, out=flank_out[i])
 
-            rounds, t_launch, t_pass, t_flank = 5, [], [], {D: [] for D in a.flanks}
+            edit_out = [torch.empty(max(ac.edit_words(s.n_kmers, args.k), 1) if a.edits else 1, dtype=torch.int32, device="cuda")
+                        for s in segs]
+
+            def the_edit_pass():
+                for i in live:
+                    c.hit_edit_profile(args.k, segs[i].kmers, segs[i].n_kmers, segs[i], wlen[i], tops[i], pos[i], starts[i],
+                                       segs[i].n_windows, out=edit_out[i])
+
+            rounds, t_launch, t_pass, t_flank, t_edit = 5, [], [], {D: [] for D in a.flanks}, []
             for r in range(rounds):  # a round: the launch's calls, then the pass's, on the same box minutes apart at most
                 for call, into in ((lambda: c.count_device(args.k, arr, window_len=wlen, hits=hits, positions=pos), t_launch),
-                                   (the_pass, t_pass)) + tuple((lambda D=D: the_flank_pass(D), t_flank[D]) for D in a.flanks):
+                                   (the_pass, t_pass)) + tuple((lambda D=D: the_flank_pass(D), t_flank[D]) for D in a.flanks) \
+                        + (((the_edit_pass, t_edit),) if a.edits else ()):
                     for i in range(a.warmup + a.launches):
                         if i == a.warmup:
                             t0.record()
@@ -334,6 +348,22 @@ def main():
                       f"(rounds: {', '.join(f'{x:.4f}' for x in t_flank[D])}), launch {ml:.4f} ms, span pass {mp:.4f} ms, "
                       f"ratio to the launch {mf / ml:.3f}; 17 planes = {planes_b} bytes, {floor:.5f} ms at 6.29 TB/s, "
                       f"{floor / mf * 100:.2f} % of the pass's time")
+            if a.edits:
+                me, obs, edits_seen = sum(t_edit) / rounds, 0, 0
+                the_edit_pass()
+                for i in live:
+                    s = segs[i]
+                    ed = edit_out[i][: ac.edit_words(s.n_kmers, args.k)].view(s.n_kmers, args.k, 12).to(torch.int64)
+                    lc = c.hit_level_counts(tops[i], s.n_kmers, s.n_windows, 1).to(torch.int64)
+                    # every hit window aligns every base of the k-mer: match, substitution or deletion
+                    assert bool((ed[:, :, :7].sum(dim=2) == lc[0][:, None]).all()), "a base's operations are not the level count"
+                    obs += int(ed.sum())
+                    edits_seen += int(ed[:, :, 1:].sum())
+                print(f"edit pass, k {args.k} E {E}: {obs} observations ({edits_seen} edits) of {hit_pairs} pairs; pass {me:.4f} ms "
+                      f"(rounds: {', '.join(f'{x:.4f}' for x in t_edit)}), launch {ml:.4f} ms, span pass {mp:.4f} ms"
+                      + "".join(f", flank pass D {D} {sum(t_flank[D]) / rounds:.4f} ms" for D in a.flanks)
+                      + f"; ratio to the span pass {me / mp:.3f}, to the launch {me / ml:.3f}; "
+                      f"{obs / me / 1e6:.3f} G observations/s, {hit_pairs / me / 1e6:.3f} G pairs/s")
         if a.positions and a.profile:
             s0 = segs[0]
             for i in range(a.warmup + a.launches):
