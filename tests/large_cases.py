@@ -11,7 +11,8 @@ Dense image: equal windows drawn from a dictionary (tests/cases.py dictionary_ca
 bases, each with the oracle's count vector).  The texts are packed once into a (61, S / 16) code table and
 a (61, S / 32) N table (S = the slot, L rounded up to 32 bases); an index tensor `idx` says which text
 every window holds and image = table[idx].  Expected counts are bincount(idx) @ per_text; expected hit,
-position and start matrices are the per-text rows expanded by the same idx.  The windows at every boundary
+position and start matrices are the per-text rows expanded by the same idx; expected flank and edit profiles are the
+per-text profiles summed through bincount(idx).  The windows at every boundary
 hold MARKER texts -- a nonzero count vector that no other text has -- so a boundary window that is skipped,
 or counted in a neighbour's place, changes the sums.
 
@@ -213,6 +214,58 @@ def text_rows(k, n_kmers, L, E):
     i32 = lambda a: np.ascontiguousarray(a, np.uint32).view(np.int32)  # noqa: E731
     return {"hits": i32(pack_hits(hit)), "pos": i32(pack_positions(pos)), "start": i32(pack_starts(start, hit[E])),
             "hit": hit, "prof": prof}
+
+
+PROFILE_DEPTHS = (8, 32)  # 32: the depth at which hit_flank.h fl_run takes three code words
+
+
+@functools.lru_cache(maxsize=None)
+def text_profiles(k, n_kmers, L, E):
+    """Per-text flank and edit profiles at edit budget E, each text alone with its own hits, end positions and
+    starts_of starts (the CPU references of the flank and edit tests): dict of
+      flank[D, plane, with_start] uint64 (n_texts, 2, n_kmers, D, 5)   D in PROFILE_DEPTHS, plane in (0, E);
+                                                                       without starts the left half is zeros
+      edit[plane]                 uint64 (n_texts, n_kmers, k, 12)
+      hit bool (E + 1, n_texts, n_kmers), pos / start int16 (n_texts, n_kmers)
+      counted bool (n_texts, n_kmers): the top-level pairs that meet the edit pass's conditions.
+    An image's expected profile is image_profile(bincount(idx), per_text): a cell is at most the window count."""
+    from tests.edit_cases import alignments
+    from tests.flank_cases import flank_profile_of
+
+    km, texts, _, _ = dense_dictionary(k, n_kmers, L)
+    hit, pos, _ = expected_positions(k, km, texts, E)
+    start, _ = starts_of(k, km, texts, hit, pos)
+    one = lambda a, t: a[t:t + 1]  # noqa: E731
+    flank, edit = {}, {}
+    counted = np.zeros(hit.shape[1:], bool)
+    for plane in (0, E):
+        al = [alignments(k, km, one(texts, t), one(hit[plane], t), one(pos, t), one(start, t)) for t in range(len(texts))]
+        edit[plane] = np.stack([a["profile"] for a in al]).astype(np.uint64)
+        if plane == E:
+            for t, a in enumerate(al):
+                counted[t, a["cs"]] = a["counted"]
+        for D in PROFILE_DEPTHS:
+            for with_start in (True, False):
+                flank[D, plane, with_start] = np.stack(
+                    [flank_profile_of(one(texts, t), one(hit[plane], t), one(pos, t), one(start, t) if with_start else None, D)
+                     for t in range(len(texts))]).astype(np.uint64)
+    return {"flank": flank, "edit": edit, "hit": hit, "pos": pos, "start": start, "counted": counted}
+
+
+def image_profile(n, per_text):
+    """The profile of an image whose texts occur n = text_counts(idx, ...) times: uint64, exact."""
+    return np.einsum("t,t...->...", n.astype(np.uint64), per_text.astype(np.uint64))
+
+
+def first_cell(got, want, axes):
+    """None if got == want, else a message naming the first differing cell by its axes."""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape, (got.shape, want.shape)
+    bad = np.argwhere(got != want)
+    if not len(bad):
+        return None
+    at = tuple(int(x) for x in bad[0])
+    return f"{len(bad)} cells differ, first at {dict(zip(axes, at))}: got {int(got[at])} want {int(want[at])}"
 
 
 # ---- the sparse image ----

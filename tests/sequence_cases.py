@@ -19,9 +19,11 @@ Launch kinds (each one call that reaches count_launch.cpp launch()):
   hits_jobs  window_hits_jobs                                                               bshs
   pos_jobs   window_hits_jobs(positions=True)                                               bsps
   submit     submit_jobs into a device tensor, alternately with and without hits=           submit scratch, slot sets
+  profiles   window_hits(spans= / flanks= / edits=) over uploads: the count launch, then     bsp, then hit_span,
+             the span, flank and edit passes per job on the context's stream                hit_flank, hit_edit
 
-The walk: an Eulerian circuit of the complete digraph on the 11 kinds (110 transitions, a fixed seed orders the
-edges), cut into segments of 11 transitions.  A segment begins with a launch of the kind the previous one ended
+The walk: an Eulerian circuit of the complete digraph on the 12 kinds (132 transitions, a fixed seed orders the
+edges), cut into segments of 12 transitions.  A segment begins with a launch of the kind the previous one ended
 with, so the cut itself is a self-pair; kinds that got no self-pair that way get one inside a segment.  A segment
 run alone on a fresh context is a valid sequence: it starts by setting the budget of its first launch, and the
 reductions before its first hits launch read matrices uploaded from the host.
@@ -30,30 +32,42 @@ reductions before its first hits launch read matrices uploaded from the host.
 
 Expected values are the existing ones, cached per shape: oracle.count_myers (E = 2), tests.test_budget_cpu.count_e
 (other budgets), tests.hits_cases.expected_hits, tests.positions_cases.expected_positions / profile_of, numpy's
-H^T H, oracle.host_ref for the exact count."""
+H^T H, oracle.host_ref for the exact count, tests.span_cases.starts_of, tests.flank_cases.flank_profile_of and
+tests.edit_cases.edit_profile_of.
+
+The span, flank and edit passes added three grow-only blocks to the context (d_start, d_flank, d_edit), carved
+per job at 256-byte offsets like the hit and position blocks, which the jobs stage carves too.  block_needs()
+below says what each launch takes of them; tests/test_sequence_cases.py runs a model of the blocks over the walk."""
 import collections
 import functools
 import random
 
 import numpy as np
 
-KINDS = ("wm", "bs", "hits", "pos", "samples", "wm_jobs", "bs_jobs", "dp_jobs", "hits_jobs", "pos_jobs", "submit")
-HIT_KINDS = ("hits", "pos", "hits_jobs", "pos_jobs")
+KINDS = ("wm", "bs", "hits", "pos", "samples", "wm_jobs", "bs_jobs", "dp_jobs", "hits_jobs", "pos_jobs", "submit",
+         "profiles")
+HIT_KINDS = ("hits", "pos", "hits_jobs", "pos_jobs", "profiles")
 JOBS_KINDS = ("wm_jobs", "bs_jobs", "dp_jobs", "hits_jobs", "pos_jobs", "submit")  # the jobs stage: staged when early
 BS_K = (16,) + tuple(range(18, 33))  # the bit-sliced kernel's pattern lengths
 SEED = 20240611
 
 # Side operations: no count kernel, but they use or change context state.  set_max_errors is placed by the
 # budget plan, the others by place_sides().
-REFUSALS = ("refuse_ragged_hits", "refuse_pos_without_hits", "refuse_budget_k", "refuse_levels5")
+REFUSALS = ("refuse_ragged_hits", "refuse_pos_without_hits", "refuse_budget_k", "refuse_levels5", "refuse_profiles")
 SIDES = ("exact_packed", "exact_uploaded", "level_counts", "position_profile", "window_counts", "cooc", "cross",
-         "cooc_host", "cross_host", "reupload", "empty") + REFUSALS
+         "cooc_host", "cross_host", "reupload", "empty", "spans_device", "flanks_device", "edits_device") + REFUSALS
 BETWEEN_GROUP_SIZES = REFUSALS + ("empty",)  # each at least once between two launches of different group size
+PER_GAP = 2  # side operations per gap: enough to put all 19 before every one of the 12 kinds (asserted on the CPU)
+# The profiles kind's variants, in turn: window_hits(spans=True), (flanks=D), (edits=True), (flanks=D, edits=True);
+# D is 8 and, at every other round of the four, 32: the depth at which hit_flank.h fl_run takes three code words.
+PROFILE_VARIANTS = ("spans", "flanks", "edits", "flanks_edits")
+DEPTHS = (8, 32)
 
 Shape = collections.namedtuple("Shape", "k jobs")
 # a job: (n_kmers, n_windows, L, n) -- L an int (equal windows) or (lo, hi) (ragged ones); n the share of N
 # bases, or "records": tests.test_gpu_bitslice.n_windows_case with 0..7 N per window, so that inline N records
-# (nrec.h: up to 4 positions) are empty, full and overflowed.  A job without k-mers or without windows is dead.
+# (nrec.h: up to 4 positions) are empty, full and overflowed; or "planted_n" (START_GROW below).  A job without
+# k-mers or without windows is dead.
 
 # word-parallel, resident: group sizes 192 (k = 10), 64 (k = 17), 256 (k = 16); 1, 3 and 6 groups; windows on
 # both sides of 32 and 128 bases
@@ -70,6 +84,15 @@ WM_SHAPES = (
 # resident wave count is -- while every other shape stays below it (at most 6 groups x 32 sub-queues, or 32 x 8).
 ACC_GROW = Shape(17, ((2000, 3, (60, 90), 0.01),))
 QUEUE_GROW = Shape(17, ((16640, 3, (60, 90), 0.01),))
+# The start block's growth (capi.cpp count_samples grows d_start by the position matrices' bytes, apart from d_pos).
+# By rotation the first profiles visit is the largest (HIT_SHAPES[1]: 13,120 + 576 bytes of positions in two jobs,
+# 14,080 at 256-byte offsets), so no later one would grow the block.  START_GROW takes 16,000 + 1,280 bytes (17,408):
+# the pos_jobs visit START_GROW_AT["pos_jobs"] grows d_pos with it, and the next profiles visit,
+# START_GROW_AT["profiles"] (an edits variant), then needs a start block larger than any before while d_pos is large
+# enough already.  Its first job's last 8 windows are tests.edit_cases.planted_windows -- a k-mer with an N in place
+# of, or inserted before, its middle base -- since no other shape of the walk holds an inserted N.
+START_GROW = Shape(16, ((300, 50, 100, "planted_n"), (40, 20, 100, 0.0)))
+START_GROW_AT = {"pos_jobs": 9, "profiles": 10}  # the kind's nth visit
 WM_JOBS_SHAPES = (  # staged group sizes 256 (k = 16), 128 (k = 17), 192 (k = 10); job regions below and above
     Shape(16, ((120, 60, (90, 110), 0.01),)),                                              # a 4096-byte chunk
     Shape(17, ((200, 30, (20, 40), 0.02), (40, 0, (20, 40), 0.0), (10, 5, (130, 200), 0.0))),
@@ -103,7 +126,8 @@ SAMPLE_STATES = (
 )
 TABLES = {"wm": WM_SHAPES, "bs": BS_SHAPES, "hits": HIT_SHAPES, "pos": HIT_SHAPES, "samples": SAMPLE_STATES,
           "wm_jobs": WM_JOBS_SHAPES, "bs_jobs": BS_SHAPES, "dp_jobs": BS_SHAPES, "hits_jobs": HIT_SHAPES,
-          "pos_jobs": HIT_SHAPES, "submit": None}  # submit: HIT_SHAPES with hits=, BS_SHAPES without, alternately
+          "pos_jobs": HIT_SHAPES, "submit": None,  # submit: HIT_SHAPES with hits=, BS_SHAPES without, alternately
+          "profiles": HIT_SHAPES}
 FIRST = {kind: i for i, kind in enumerate(KINDS)}  # where in its table a kind starts, so that no two run in step
 # host-buffer co-occurrence shapes (n_kmers, n_windows) and cross ones (n_a, n_b, n_windows): small, larger, small
 COOC_HOST = ((130, 257), (600, 1100), (33, 64))
@@ -151,6 +175,19 @@ Visit = collections.namedtuple("Visit", "n kind nth shape E with_hits wh segment
 # wh: a samples visit that also calls window_hits
 
 
+def profile_args(v):
+    """(spans, flanks, edits) of a profiles visit's window_hits call: the variants in turn by the kind's nth visit,
+    D = 8 in the first round of four, 32 in the second, and so on."""
+    variant = PROFILE_VARIANTS[v.nth % 4]
+    D = DEPTHS[v.nth // 4 % 2] if "flanks" in variant else 0
+    return variant == "spans", D, "edits" in variant
+
+
+def pos_spans(v):
+    """A pos visit that also passes spans= (every other one)."""
+    return v.kind == "pos" and v.nth % 2 == 1
+
+
 def euler_circuit(n, seed):
     """An Eulerian circuit of the complete digraph on n nodes without loops (Hierholzer; the seed orders every
     node's out-edges): n (n - 1) + 1 nodes, the first again at the end."""
@@ -170,11 +207,12 @@ def euler_circuit(n, seed):
 
 
 def build_segments():
-    """Lists of kinds: the circuit in runs of 11 transitions, each run beginning with the previous one's last
-    kind again; then a self-pair inside a segment for every kind without one, and for two bit-sliced kinds in any
-    case (the budget changes between two launches of one kind and k)."""
-    nodes = [KINDS[i] for i in euler_circuit(len(KINDS), SEED)]
-    segs = [nodes[i:i + 12] for i in range(0, len(nodes) - 1, 11)]
+    """Lists of kinds: the circuit in runs of len(KINDS) transitions, each run beginning with the previous one's
+    last kind again; then a self-pair inside a segment for every kind without one, and for two bit-sliced kinds in
+    any case (the budget changes between two launches of one kind and k)."""
+    n = len(KINDS)
+    nodes = [KINDS[i] for i in euler_circuit(n, SEED)]
+    segs = [nodes[i:i + n + 1] for i in range(0, len(nodes) - 1, n)]
     have = {segs[i][0] for i in range(1, len(segs))}
     need = [k for k in KINDS if k not in have]
     need += [k for k in ("bs", "hits_jobs") if k not in need]
@@ -196,7 +234,7 @@ def shape_of(kind, nth, with_hits):
 
 
 def build_walk():
-    """The launch visits, segment by segment: shapes by rotation, the two growth visits, then the budget of every
+    """The launch visits, segment by segment: shapes by rotation, the growth visits, then the budget of every
     visit -- greedily the one that adds an uncovered change E -> E' or an uncovered (kind, E)."""
     segs = build_segments()
     nth = collections.Counter()
@@ -213,6 +251,8 @@ def build_walk():
                 shape, with_hits = visits[-1].shape, visits[-1].with_hits
             elif kind == "wm" and grow and i > 0 and v >= 3 and (len(grow) == 2 or v >= 7):
                 shape = grow.pop(0)
+            elif START_GROW_AT.get(kind) == v:
+                shape = START_GROW
             wh = kind == "samples" and is_bs(kind, shape)  # window_hits too, wherever it is legal
             visits.append(Visit(len(visits), kind, v, shape, None, with_hits, wh, s))
     assert not grow
@@ -239,8 +279,8 @@ def build_walk():
 
 
 def place_sides(visits):
-    """sides[n]: the side operations in the gap before launch n (none before a segment's first launch) -- two per
-    gap, those the following kind has not had yet first; refuse_budget_k only where the context's budget is not 2;
+    """sides[n]: the side operations in the gap before launch n (none before a segment's first launch) -- PER_GAP
+    per gap, those the following kind has not had yet first; refuse_budget_k only where the context's budget is not 2;
     in a gap between two group sizes, the operations that still need such a gap first."""
     had = collections.defaultdict(set)
     total = collections.Counter()
@@ -252,7 +292,7 @@ def place_sides(visits):
         diff = launch_groups(prev.kind, prev.shape)[0] != launch_groups(v.kind, v.shape)[0]
         ok = [s for s in SIDES if s != "refuse_budget_k" or prev.E != 2]
         ok.sort(key=lambda s: (not (diff and s in need_diff), s in had[v.kind], total[s], SIDES.index(s)))
-        pick = ok[:2]
+        pick = ok[:PER_GAP]
         for s in pick:
             had[v.kind].add(s)
             total[s] += 1
@@ -308,6 +348,12 @@ def case(shape, j):
         km, w = n_windows_case(seed, nw, L, [0, 1, 5, 0, 6, 4, 7], (0, 15, 16, 31, 32, 99))
         assert shape.k == 16 and nk == len(km)
         return np.asarray(km, np.uint64), w
+    if n == "planted_n":
+        from tests.edit_cases import planted_windows
+
+        km, w = budget_case(seed, shape.k, nk, nw - 8, L, p_n=0.01)
+        km = np.asarray(km[:nk], np.uint64)
+        return km, list(w) + planted_windows(seed + 1, shape.k, [int(x) for x in km], 8, L)
     if not nw:
         return np.asarray(cases.planted_case(seed, shape.k, nk, 0)[0], np.uint64), []
     if isinstance(L, int):
@@ -337,6 +383,47 @@ def expected_matrices(shape, j, E):
 
     km, w = case(shape, j)
     return expected_positions(shape.k, km, w, E)
+
+
+@functools.lru_cache(maxsize=None)
+def expected_starts(shape, j, E):
+    """int16 (n_windows, n_kmers) of job j: where each pair's best occurrence starts (tests.span_cases.starts_of),
+    -1 where there is no hit."""
+    from tests.span_cases import starts_of
+
+    km, w = case(shape, j)
+    hit, pos, _ = expected_matrices(shape, j, E)
+    start = starts_of(shape.k, km, w, hit, pos)[0]
+    start.setflags(write=False)
+    return start
+
+
+def packed_starts(shape, j, E):
+    """The start matrix of job j in the matrix layout, uint32 (8, n_windows, words)."""
+    from tests.span_cases import pack_starts
+
+    return pack_starts(expected_starts(shape, j, E), expected_matrices(shape, j, E)[0][E])
+
+
+@functools.lru_cache(maxsize=None)
+def expected_flanks(shape, j, E, D, plane=None, with_start=True):
+    """uint32 (2, n_kmers, D, 5) of job j over level plane `plane` (None: the top one, E), with the expected
+    starts or with start = None (the left half zeros): tests.flank_cases.flank_profile_of."""
+    from tests.flank_cases import flank_profile_of
+
+    hit, pos, _ = expected_matrices(shape, j, E)
+    start = expected_starts(shape, j, E) if with_start else None
+    return flank_profile_of(case(shape, j)[1], hit[E if plane is None else plane], pos, start, D)
+
+
+@functools.lru_cache(maxsize=None)
+def expected_edits(shape, j, E, plane=None):
+    """uint32 (n_kmers, k, 12) of job j over level plane `plane` (None: the top one): tests.edit_cases.edit_profile_of."""
+    from tests.edit_cases import edit_profile_of
+
+    km, w = case(shape, j)
+    hit, pos, _ = expected_matrices(shape, j, E)
+    return edit_profile_of(shape.k, km, w, hit[E if plane is None else plane], pos, expected_starts(shape, j, E))
 
 
 @functools.lru_cache(maxsize=None)
@@ -378,3 +465,48 @@ def matrix_after(visits):
         if v.kind in HIT_KINDS or (v.kind == "submit" and v.with_hits) or v.wh:
             m = (v.shape, next(j for j, x in enumerate(v.shape.jobs) if live(x)), v.E)
     return m
+
+
+def flanks_side(i):
+    """(with the start matrix, over the top plane, D) of the flanks_device operation's i-th use."""
+    return i % 2 == 0, i // 2 % 2 == 0, DEPTHS[i // 4 % 2]
+
+
+def edits_side(i):
+    """Whether the edits_device operation's i-th use reads the top plane (else plane 0)."""
+    return i % 2 == 0
+
+
+# ---- the context's matrix blocks -----------------------------------------------------------------------------------
+
+def align256(n):
+    return (n + 255) // 256 * 256
+
+
+def block_needs(v):
+    """What launch v carves out of the context's grow-only matrix blocks at default settings, or None where it
+    uses none: {block: bytes per job}.  capi.cpp count_samples (profiles, and a samples visit's window_hits) and
+    jobs_stage.cpp count_jobs (hits_jobs, pos_jobs) carve `hits` and `pos` -- every job's matrix, a dead job's
+    being empty; count_samples alone `start` (the position matrices' sizes and offsets, but a block of its own),
+    `flank` and `edit` (live jobs only).  hits, pos and submit visits write the caller's tensors."""
+    if v.kind == "profiles":
+        spans, D, edits = profile_args(v)
+        with_pos = True
+    elif v.kind == "samples" and v.wh:
+        spans, D, edits, with_pos = False, 0, False, v.nth % 2 == 1
+    elif v.kind in ("hits_jobs", "pos_jobs"):
+        spans, D, edits, with_pos = False, 0, False, v.kind == "pos_jobs"
+    else:
+        return None
+    jobs, k = v.shape.jobs, v.shape.k
+    words = [j[1] * ((j[0] + 31) // 32) for j in jobs]
+    need = {"hits": [4 * (v.E + 1) * w for w in words]}
+    if with_pos:
+        need["pos"] = [4 * 8 * w for w in words]
+    if v.kind == "profiles":
+        need["start"] = need["pos"]
+        if D:
+            need["flank"] = [4 * 2 * j[0] * D * 5 if live(j) else 0 for j in jobs]
+        if edits:
+            need["edit"] = [4 * j[0] * k * 12 if live(j) else 0 for j in jobs]
+    return need

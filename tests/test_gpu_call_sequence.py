@@ -10,6 +10,11 @@ ran, the stage mode where the kind fixes it, and the candidate groups tests/test
 that the walk reached what it set out to reach.  After every refusal: AC_ERR_INVALID, a message that names the
 constraint, the filled buffers untouched, and a clean check().
 
+The span, flank and edit passes are in the walk three ways: the `profiles` kind (window_hits(spans= / flanks= /
+edits=), whose per-job matrices and profiles the context carves out of grow-only blocks), every other `pos` visit
+(count_device(..., spans=)), and side operations that run each pass alone over the matrices the last hits launch
+left, with start positions from the CPU reference.
+
 With AC_BITSLICE=0 in the environment no launch is bit-sliced: the hits kinds and every launch at a budget other
 than 2 are then refusals themselves, and the rest of the walk still runs."""
 import ctypes
@@ -94,15 +99,53 @@ def raw_refused(c, status, word, bufs=()):
     c.check()
 
 
+def device_segment(shape, j):
+    km, w = sc.case(shape, j)
+    return ac.DeviceSegment.upload(km, ac.pack_windows(w))
+
+
+def host_buffers(c, k, km, smp, D):
+    """The host matrices and profiles of one job of ac_window_*_samples, each filled and GUARD words longer."""
+    nk, nw = len(km), smp.n_windows
+    sizes = {"hits": ac.hits_words(nk, nw, c.max_errors), "pos": ac.positions_words(nk, nw),
+             "start": ac.positions_words(nk, nw), "flank": ac.flank_words(nk, D), "edit": ac.edit_words(nk, k)}
+    return {name: np.full(n + GUARD, FILL, np.uint32) for name, n in sizes.items()}
+
+
+def raw_window_profiles(c, k, parts, packed, D, edits):
+    """upload_sample into slot j, then the entry point window_hits(spans= / flanks= / edits=) calls, over host
+    buffers of 0xFFFFFFFF with GUARD words more: (status, [counts per job], [host_buffers per job])."""
+    u64 = ctypes.POINTER(ctypes.c_uint64)
+    kms, counts, bufs, jobs = [], [], [], []
+    for slot, ((km, _), smp) in enumerate(zip(parts, packed)):
+        km = np.ascontiguousarray(km, np.uint64)
+        kms.append(km if km.size else np.zeros(1, np.uint64))
+        counts.append(np.full(km.size + 1, 0xFFFFFFFFFFFFFFFF, np.uint64))
+        bufs.append(host_buffers(c, k, km, smp, D))
+        jobs.append(_lib.ACSampleJob(kms[-1].ctypes.data_as(u64), km.size, c.upload_sample(smp, slot),
+                                     counts[-1].ctypes.data_as(u64)))
+    arr = (_lib.ACSampleJob * len(jobs))(*jobs)
+    ptrs = lambda name: (_lib.p32 * len(jobs))(*[b[name].ctypes.data_as(_lib.p32) for b in bufs])  # noqa: E731
+    mats = (ptrs("hits"), ptrs("pos"), ptrs("start"))
+    if edits:
+        st = c._L.ac_window_edits_samples(c.handle, k, arr, len(jobs), D, *mats, ptrs("flank") if D else None, ptrs("edit"))
+    elif D:
+        st = c._L.ac_window_flanks_samples(c.handle, k, arr, len(jobs), D, *mats, ptrs("flank"))
+    else:
+        st = c._L.ac_window_spans_samples(c.handle, k, arr, len(jobs), *mats)
+    return st, counts, bufs
+
+
 class Run:
     """One context's walk: the context, and what the side operations read -- the hit matrices the last hits or
-    positions launch left (before any: HIT_SHAPES[0] at E = 2, uploaded from the host) and the sample last
-    uploaded into slot 0."""
+    positions launch left (before any: HIT_SHAPES[0] at E = 2, uploaded from the host), the k-mers and window
+    image of that job on the device, and the sample last uploaded into slot 0."""
 
     def __init__(self, c, two_parts=False):
         self.c, self.two_parts, self.jobs_calls = c, two_parts, 0
         hit, pos, _ = sc.expected_matrices(sc.HIT_SHAPES[0], 0, 2)
         self.mat = (sc.HIT_SHAPES[0], 0, 2, to_device(pack_hits(hit)), to_device(pack_positions(pos)))
+        self.seg = device_segment(sc.HIT_SHAPES[0], 0)
         self.uploaded = (sc.SAMPLE_STATES[0], 0)
 
     # ---- launches ----
@@ -112,10 +155,12 @@ class Run:
 
     def keep(self, v, d_hits, d_pos):
         """The first live job's matrices are what the reductions read next (positions the launch did not write
-        come from the expected ones)."""
+        come from the expected ones), with its k-mers and windows on the device for the span, flank and edit
+        passes."""
         j = next(i for i, x in enumerate(v.shape.jobs) if sc.live(x))
         pos = d_pos[j] if d_pos is not None else to_device(pack_positions(sc.expected_matrices(v.shape, j, v.E)[1]))
         self.mat = (v.shape, j, v.E, d_hits[j], pos)
+        self.seg = device_segment(v.shape, j)
 
     def reached(self, v, kernel, mode=None, groups=True):
         c = self.c
@@ -172,9 +217,12 @@ class Run:
         if v.kind == "pos":
             pb = [filled(ac.positions_words(s.n_kmers, s.n_windows)) if sc.live(j) else None
                   for s, j in zip(segs, v.shape.jobs)]
-        call = lambda: c.count_device(k, segs, window_len=lens, hits=hb, positions=pb)  # noqa: E731
+        sb = None
+        if sc.pos_spans(v):  # (a dead segment's tensor must stay as it is: the span pass skips it)
+            sb = [filled(ac.positions_words(s.n_kmers, s.n_windows) if sc.live(j) else 8) for s, j in zip(segs, v.shape.jobs)]
+        call = lambda: c.count_device(k, segs, window_len=lens, hits=hb, positions=pb, spans=sb)  # noqa: E731
         if v.kind != "wm" and not BS_ON and (hb is not None or E != 2):
-            return self.refused_launch(v, call, [s.counts for s in segs] + (hb or []) + (pb or []))
+            return self.refused_launch(v, call, [s.counts for s in segs] + (hb or []) + (pb or []) + (sb or []))
         call()
         torch.cuda.synchronize()
         c.check()
@@ -193,6 +241,11 @@ class Run:
             if pb is not None:
                 planes = take(pb[j], ac.positions_words(s.n_kmers, s.n_windows), (8, s.n_windows, words(s)), "positions")
             self.compare_matrices(v, j, counts, levels, planes)
+            if sb is not None:
+                starts = take(sb[j], ac.positions_words(s.n_kmers, s.n_windows), (8, s.n_windows, words(s)), "starts")
+                same(starts, sc.packed_starts(v.shape, j, E), (v.kind, v.n, j, "start words"))
+        if sb is not None:
+            assert untouched([t for t, job in zip(sb, v.shape.jobs) if not sc.live(job)]), "a dead segment's starts"
         if hb is not None:
             self.keep(v, hb, pb)
 
@@ -224,6 +277,69 @@ class Run:
                 assert not wh[j].counts.any()
         j = next(i for i, x in enumerate(v.shape.jobs) if sc.live(x))
         self.keep(v, {j: to_device(wh[j].levels)}, {j: to_device(wh[j].planes)} if positions else None)
+
+    def compare_profiles(self, v, j, D, edits, starts, flanks, edit_prof):
+        """The start planes, and the flank and edit profiles the variant asked for, of live job j."""
+        nk = v.shape.jobs[j][0]
+        same(starts, sc.packed_starts(v.shape, j, v.E), (v.kind, v.n, j, "start words"))
+        if D:
+            same(np.asarray(flanks).reshape(2, nk, D, 5), sc.expected_flanks(v.shape, j, v.E, D),
+                 (v.kind, v.n, j, f"flank profile, D = {D}: (side, k-mer, column, symbol)"))
+        if edits:
+            same(np.asarray(edit_prof).reshape(nk, v.shape.k, 12), sc.expected_edits(v.shape, j, v.E),
+                 (v.kind, v.n, j, "edit profile: (k-mer, base, operation)"))
+
+    def launch_profiles(self, v):
+        """window_hits(spans= / flanks= / edits=): the parts are uploaded into the slots, counted in one launch,
+        and the span, flank and edit passes follow per job on the context's stream.  A shape with a dead job goes
+        through upload_sample and the entry point itself, over filled host buffers: a job without work leaves
+        them as they are."""
+        c, k, parts = self.c, v.shape.k, self.parts(v)
+        packed = [ac.pack_windows(w) for _, w in parts]
+        spans, D, edits = sc.profile_args(v)
+        self.uploaded = (v.shape, 0)
+        first = next(i for i, x in enumerate(v.shape.jobs) if sc.live(x))
+        if all(sc.live(x) for x in v.shape.jobs):
+            call = lambda: c.window_hits(k, [(km, p) for (km, _), p in zip(parts, packed)], spans=spans, flanks=D,  # noqa: E731
+                                         edits=edits)
+            if not BS_ON:
+                return self.refused_launch(v, call)
+            wh = call()
+            self.reached(v, 1)
+            for j in range(len(parts)):
+                self.compare_matrices(v, j, wh[j].counts, wh[j].levels, wh[j].planes)
+                assert (wh[j].flanks is None) == (not D) and (wh[j].edits is None) == (not edits)
+                self.compare_profiles(v, j, D, edits, wh[j].starts, wh[j].flanks, wh[j].edits)
+            self.keep(v, {first: to_device(wh[first].levels)}, {first: to_device(wh[first].planes)})
+            return
+        before = (kernel_of(c), c.last_launch(), c.max_errors)
+        st, counts, bufs = raw_window_profiles(c, k, parts, packed, D, edits)
+        if not BS_ON:
+            assert st == _lib.AC_ERR_INVALID and "AC_BITSLICE" in c._L.ac_last_error(c.handle).decode(), st
+            assert all((a == FILL).all() for b in bufs for a in b.values()), "a refused call wrote"
+            c.check()
+            assert (kernel_of(c), c.last_launch(), c.max_errors) == before
+            return
+        _lib.check(st, c.handle)
+        self.reached(v, 1)
+        used = {"hits", "pos", "start"} | ({"flank"} if D else set()) | ({"edit"} if edits else set())
+        for j, (job, b) in enumerate(zip(v.shape.jobs, bufs)):
+            nk, nw = job[:2]
+            assert counts[j][nk] == 0xFFFFFFFFFFFFFFFF, "a count past the job's k-mers"
+            if not sc.live(job):  # no work: zero counts, every host buffer as it was
+                assert not counts[j][:nk].any() and all((a == FILL).all() for a in b.values()), (v.n, j)
+                continue
+            words = (nk + 31) // 32
+            shapes = {"hits": (v.E + 1, nw, words), "pos": (8, nw, words), "start": (8, nw, words),
+                      "flank": (2, nk, D, 5), "edit": (nk, k, 12)}
+            got = {}
+            for name, a in b.items():
+                n = int(np.prod(shapes[name]))
+                assert (a[n if name in used else 0:] == FILL).all(), (v.n, j, name, "a store past the end, or into a buffer not asked for")
+                got[name] = a[:n].reshape(shapes[name])
+            self.compare_matrices(v, j, counts[j][:nk], got["hits"], got["pos"])
+            self.compare_profiles(v, j, D, edits, got["start"], got["flank"], got["edit"])
+        self.keep(v, {first: to_device(bufs[first]["hits"][:-GUARD])}, {first: to_device(bufs[first]["pos"][:-GUARD])})
 
     def jobs_of(self, v, pinned=False):
         out = []
@@ -378,6 +494,73 @@ class Run:
         got = self.reduce(self.c._L.ac_hit_cross_cooccurrence_device, (p32(d_hits), nk, p32(top), nk, nw, 1), nk * nk,
                           (1, nk, nk), "cross")
         same(got, sc.product(hit[:1], hit[-1:]), "cross co-occurrence")
+
+    def profile_inputs(self):
+        """The matrix's job for the span, flank and edit passes: (shape, j, E, n_kmers, n_windows, L, hits, pos,
+        plane(e) -> level plane e, the expected start matrix uploaded).  The starts come from the CPU reference,
+        so that a wrong span pass cannot hide a wrong flank or edit pass."""
+        shape, j, E, d_hits, d_pos = self.mat
+        nk, nw, L = shape.jobs[j][:3]
+        size = nw * ((nk + 31) // 32)
+        return (shape, j, E, nk, nw, L, d_hits, d_pos, lambda e: d_hits[e * size:(e + 1) * size],
+                to_device(sc.packed_starts(shape, j, E)))
+
+    def device_pass(self, fn, n, shape, what):
+        """One pass into a filled, guarded output: synchronize, check(), the guard, the result."""
+        import torch
+
+        out = filled(n)
+        fn(out)
+        torch.cuda.synchronize()
+        self.c.check()
+        return take(out, n, shape, what)
+
+    def side_spans_device(self, i):
+        shape, j, E, nk, nw, L, d_hits, d_pos, _, _ = self.profile_inputs()
+        got = self.device_pass(lambda out: self.c.hit_start_positions(shape.k, self.seg.kmers, nk, self.seg, L, d_hits, d_pos,
+                                                                      E + 1, out=out),
+                               ac.positions_words(nk, nw), (8, nw, (nk + 31) // 32), "starts")
+        same(got, sc.packed_starts(shape, j, E), "span pass: start words")
+
+    def side_flanks_device(self, i):
+        """With the start matrix and with start = None (the left half zeros), over the top plane and plane 0."""
+        shape, j, E, nk, nw, L, _, d_pos, plane, d_start = self.profile_inputs()
+        with_start, top, D = sc.flanks_side(i)
+        got = self.device_pass(lambda out: self.c.hit_flank_profile(self.seg, L, plane(E if top else 0), d_pos,
+                                                                    d_start if with_start else None, nk, nw, D, out=out),
+                               ac.flank_words(nk, D), (2, nk, D, 5), "flank profile")
+        same(got, sc.expected_flanks(shape, j, E, D, None if top else 0, with_start),
+             f"flank pass, D = {D}, {'top plane' if top else 'plane 0'}, {'with' if with_start else 'no'} starts: "
+             "(side, k-mer, column, symbol)")
+        assert with_start or not got[1].any()
+
+    def side_edits_device(self, i):
+        shape, j, E, nk, nw, L, _, d_pos, plane, d_start = self.profile_inputs()
+        top = sc.edits_side(i)
+        got = self.device_pass(lambda out: self.c.hit_edit_profile(shape.k, self.seg.kmers, nk, self.seg, L,
+                                                                   plane(E if top else 0), d_pos, d_start, nw, out=out),
+                               ac.edit_words(nk, shape.k), (nk, shape.k, 12), "edit profile")
+        same(got, sc.expected_edits(shape, j, E, None if top else 0),
+             f"edit pass, {'top plane' if top else 'plane 0'}: (k-mer, base, operation)")
+
+    def side_refuse_profiles(self, i):
+        """One refusal of each of the three passes, the cases in turn (those tests/test_gpu_spans.py,
+        test_gpu_flanks.py and test_gpu_edits.py pin)."""
+        c = self.c
+        shape, j, E, nk, nw, L, d_hits, d_pos, plane, d_start = self.profile_inputs()
+        k, seg, top = shape.k, self.seg, plane(E)
+        out = filled(max(ac.positions_words(nk, nw), ac.flank_words(nk, 32), ac.edit_words(nk, 32)))
+        span = lambda kk=k, wl=L, lv=E + 1, p=d_pos: (  # noqa: E731
+            lambda: c.hit_start_positions(kk, seg.kmers, nk, seg, wl, d_hits, p, lv, out=out))
+        flank = lambda wl=L, d=8, h=top: lambda: c.hit_flank_profile(seg, wl, h, d_pos, d_start, nk, nw, d, out=out)  # noqa: E731
+        edit = lambda kk=k, wl=L, s=d_start: (  # noqa: E731
+            lambda: c.hit_edit_profile(kk, seg.kmers, nk, seg, wl, top, d_pos, s, nw, out=out))
+        for fn, word in (((span(lv=5), "levels must be 1..4"), (span(kk=33), "k must be 2..32"), (span(p=None), "hits or pos is NULL"))[i % 3],
+                         ((flank(d=33), "depth must be 1..32"), (flank(wl=257), "window_len must be 1..256"),
+                          (flank(h=None), "hit_plane or pos is NULL"))[i % 3],
+                         ((edit(wl=0), "window_len must be 1..256"), (edit(kk=33), "k must be 2..32"),
+                          (edit(s=None), "hit_plane, pos or start is NULL"))[i % 3]):
+            refused(c, fn, word, [out])
 
     def side_cooc_host(self, i):
         nk, nw = sc.COOC_HOST[i % 3]
@@ -541,14 +724,15 @@ def test_dma_route_first_two_segments():
 # ---- the command line: everything on at once, three runs on one context ---------------------------------------------
 
 def test_cli_every_extension_three_runs(tmp_path):
-    """adaptFinder on the cfg1 FASTA with --seed 1 -mr 3 --paired-sample --levels --positions --cooccurrence
-    --cross-cooccurrence --max-errors 3: three runs of upload, exact count, positions launch, co-occurrence and
-    cross on one context.  Every file of runs 1 and 2 is byte for byte run 0's, and run 0's main files are those of
+    """adaptFinder on the cfg1 FASTA with --seed 1 -mr 3 --paired-sample --levels --positions --spans --flanks 8
+    --edits --cooccurrence --cross-cooccurrence --max-errors 3: three runs of upload, exact count, positions
+    launch, span, flank and edit passes, co-occurrence and cross on one context.  Every file of runs 1 and 2 is byte for byte run 0's, and run 0's main files are those of
     the same command without the extension flags."""
     base = [CLI, os.path.join(CFG1, "reads.fa"), "-k", "16", "-sn", "1000", "-sl", "100", "-lim", "100", "--seed", "1",
             "-mr", "3", "--paired-sample", "--max-errors", "3"]
     run = lambda extra: subprocess.run(base + extra, cwd=tmp_path, capture_output=True, text=True, timeout=300)  # noqa: E731
-    r = run(["--levels", "--positions", "--cooccurrence", "--cross-cooccurrence", "-o", "all"])
+    r = run(["--levels", "--positions", "--spans", "--flanks", "8", "--edits", "--cooccurrence", "--cross-cooccurrence",
+             "-o", "all"])
     if not BS_ON:
         assert r.returncode == 1 and "AC_BITSLICE" in r.stderr
         return
@@ -557,7 +741,7 @@ def test_cli_every_extension_three_runs(tmp_path):
     assert plain.returncode == 0, plain.stderr
     names = sorted(p.name for p in tmp_path.iterdir() if p.name.startswith("all_0."))
     assert {"all_0.start", "all_0.end", "all_0.cross"} <= set(names), names
-    for ext in (".levels", ".positions", ".cooc"):
+    for ext in (".levels", ".positions", ".cooc", ".starts", ".lengths", ".flanks", ".edits"):
         assert {f"all_0.start{ext}", f"all_0.end{ext}"} <= set(names), names
     for name in names:
         first = (tmp_path / name).read_bytes()

@@ -7,7 +7,8 @@ because the edge is an address, not a length: nothing smaller reaches it.  The w
 The images are built on the device (tests/large_cases.py; tests/test_large_cases.py shows on the CPU that
 every case has the property relied on here).  Dense images hold dictionary texts, marker texts at every
 boundary window; counts are compared with bincount(idx) @ per_text, hit / position / start matrices plane by
-plane with the per-text rows of the CPU references expanded by idx.  The sparse image holds a few dozen ragged
+plane with the per-text rows of the CPU references expanded by idx, flank and edit profiles with the per-text
+profiles summed through bincount(idx).  The sparse image holds a few dozen ragged
 windows around the boundaries; counts are the oracle's.  Every launch asserts which count kernel ran.
 
 Sizes ascend within the file, so the smallest failing size is the one reported.  The module's peak device
@@ -124,7 +125,7 @@ def test_dense_bit_sliced_count(ctx, n_bases, L, k):
     count_and_accumulate(ctx, k, seg, L, lc.expected_counts(idx, per), BITSLICE, (n_bases, L, k))
 
 
-# ---- 2: dense, hits, positions and spans at the bound ----
+# ---- 2: dense, hits, positions, spans, flank and edit profiles at the bound ----
 
 def hits_launch(ctx, E):
     """The hits-and-positions launch at k = 16, 64 candidates, windows of 100 bases, the largest image, at edit
@@ -190,20 +191,84 @@ def test_dense_hits_and_positions(ctx, E):
     ctx.check()
 
 
-def test_dense_spans(ctx):
-    """The span pass over the same launch's matrices at E = 2: the eight start planes equal the per-text start
-    rows expanded by idx."""
+def span_pass(ctx, got):
+    """The span pass over hits_launch(ctx, 2)'s matrices; the eight start planes are compared with the per-text
+    start rows expanded by idx before anything uses them."""
     import torch
 
-    got = hits_launch(ctx, 2)
-    if got is None:
-        return
     seg, idx, drows, rows, n, levels, h, p = got
     start = ctx.hit_start_positions(16, seg.kmers, 64, seg, 100, h, p, 3)
     torch.cuda.synchronize()
     ctx.check()
     for b in range(8):
         assert (bad := lc.first_mismatch(start[b], drows["start"][b], idx, 128)) is None, f"start plane {b}: {bad}"
+    return start
+
+
+def test_dense_spans(ctx):
+    """The span pass over the same launch's matrices at E = 2: the eight start planes equal the per-text start
+    rows expanded by idx."""
+    got = hits_launch(ctx, 2)
+    if got is None:
+        return
+    span_pass(ctx, got)
+
+
+def test_dense_flank_profiles(ctx):
+    """The flank pass over the same matrices and the span pass's starts (134,217,695 windows x 2 word columns: a
+    window's text lies at up to base 2^34 - 4256, a plane word at up to 2^31 - 528 words into the sixteen position
+    and start planes): the top plane at D = 8 and D = 32, once without starts (the left half zeros), once plane 0
+    -- each equal to the per-text profiles summed through bincount(idx)."""
+    import torch
+
+    got = hits_launch(ctx, 2)
+    if got is None:
+        return
+    seg, idx, drows, rows, n, levels, h, p = got
+    start = span_pass(ctx, got)
+    nk, nw, L, E = 64, seg.n_windows, 100, 2
+    per = lc.text_profiles(16, nk, L, E)["flank"]
+    for D, plane, with_start in ((8, E, True), (32, E, True), (8, E, False), (8, 0, True)):
+        out = ctx.hit_flank_profile(seg, L, h[plane], p, start if with_start else None, nk, nw, D)
+        torch.cuda.synchronize()
+        ctx.check()
+        prof = out.cpu().numpy().view(np.uint32)
+        want = lc.image_profile(n, per[D, plane, with_start])
+        assert want.any() and want.max() <= nw < 1 << 32
+        bad = lc.first_cell(prof, want, ("side", "k-mer", "column", "symbol"))
+        assert bad is None, f"flank profile, D = {D}, plane {plane}, {'with' if with_start else 'no'} starts: {bad}"
+        assert with_start or not prof[1].any()
+        del out
+    ctx.check()
+
+
+def test_dense_edit_profiles(ctx):
+    """The edit pass over the same matrices and starts: the top plane and plane 0 equal the per-text profiles summed
+    through bincount(idx), and for every k-mer and base the operations 0..6 (match, five substitutions, deletion)
+    sum to the k-mer's pairs in the plane -- every pair of the dictionary meets the pass's conditions."""
+    import torch
+
+    got = hits_launch(ctx, 2)
+    if got is None:
+        return
+    seg, idx, drows, rows, n, levels, h, p = got
+    start = span_pass(ctx, got)
+    nk, nw, L, E, k = 64, seg.n_windows, 100, 2, 16
+    per = lc.text_profiles(k, nk, L, E)["edit"]
+    for plane in (E, 0):
+        out = ctx.hit_edit_profile(k, seg.kmers, nk, seg, L, h[plane], p, start, nw)
+        torch.cuda.synchronize()
+        ctx.check()
+        prof = out.cpu().numpy().view(np.uint32)
+        want = lc.image_profile(n, per[plane])
+        assert want.any() and want.max() <= nw < 1 << 32
+        bad = lc.first_cell(prof, want, ("k-mer", "base", "operation"))
+        assert bad is None, f"edit profile, plane {plane}: {bad}"
+        pairs = np.repeat(levels[plane][:, None], k, axis=1)
+        bad = lc.first_cell(prof[:, :, :7].sum(axis=2, dtype=np.uint64), pairs, ("k-mer", "base"))
+        assert bad is None, f"edit profile, plane {plane}: operations 0..6 against the k-mer's pairs: {bad}"
+        del out
+    ctx.check()
 
 
 # ---- 3: dense, the word-parallel kernel ----

@@ -1,7 +1,8 @@
 """CPU companion of tests/test_gpu_large_image.py: on a scaled-down image built by the same functions
 (tests/large_cases.py, numpy path) every case has the property its GPU test relies on -- the bincount formula
 gives the oracle's counts, every boundary window holds a marker text whose loss changes the sums, the expanded
-per-text rows are the references' matrices, the sparse windows sit where the docstrings say -- and the window
+per-text rows are the references' matrices, the per-text flank and edit profiles summed through bincount(idx) are
+the references' profiles and change under an index fault, the sparse windows sit where the docstrings say -- and the window
 index arithmetic names the code bytes it claims to."""
 import numpy as np
 import pytest
@@ -136,6 +137,77 @@ def test_expanded_rows_are_the_references_matrices(E):
     broken[200, 1] ^= 4
     msg = lc.first_mismatch(broken, rows["hits"][E], idx, S)
     assert msg.startswith(f"window 200 (code byte {200 * S // 4:#x}, text {int(idx[200])})"), msg
+
+
+def test_dictionary_profiles_are_not_trivial():
+    """What tests/test_gpu_large_image.py's flank and edit tests rely on in the (16, 64, 100) dictionary at E = 2,
+    so that a change of dictionary cannot empty them."""
+    k, n_kmers, L, E = 16, 64, 100, 2
+    km, texts, per, markers = lc.dense_dictionary(k, n_kmers, L)
+    p = lc.text_profiles(k, n_kmers, L, E)
+    hit, pos, start = p["hit"], p["pos"], p["start"]
+    top = hit[E]
+    dist = (E + 1 - hit.sum(axis=0))
+    assert len(texts) == 61 and int(top.any(axis=1).sum()) == 48
+    assert [int(((dist == d) & top).any(axis=1).sum()) for d in range(E + 1)] == [12, 18, 18]
+    assert len(markers) == 36
+    for name, a in (("flank, D = 8", p["flank"][8, E, True]), ("flank, D = 32", p["flank"][32, E, True]), ("edit", p["edit"][E])):
+        a = a.reshape(len(texts), -1)
+        for t in markers:  # a nonzero profile that no other text has
+            assert a[t].any() and int((a == a[t]).all(axis=1).sum()) == 1, (name, t)
+    assert p["edit"][E].sum(axis=(0, 1, 2)).tolist() == [727, 5, 8, 3, 6, 10, 9, 1, 4, 3, 3, 2]
+    assert p["counted"][top].all() and not p["counted"][~top].any()  # no pair fails the edit pass's conditions
+    assert int((pos[top].astype(int) + 8 > L).sum()) == 18 and int((start[top] < 8).sum()) == 18  # cut at D = 8
+    # the other forms the GPU tests run: plane 0 holds fewer pairs, and without starts only the left half goes
+    assert 0 < p["edit"][0].sum() < p["edit"][E].sum() and 0 < p["flank"][8, 0, True].sum() < p["flank"][8, E, True].sum()
+    for D in lc.PROFILE_DEPTHS:
+        with_s, without = p["flank"][D, E, True], p["flank"][D, E, False]
+        assert np.array_equal(with_s[:, 0], without[:, 0]) and with_s[:, 1].any() and not without[:, 1].any()
+        assert with_s.shape == (61, 2, n_kmers, D, 5)
+    assert p["flank"][32, E, True][:, :, :, 8:].any()  # (columns only the deeper profile has)
+    # operations 0..6 of a base sum to the pairs counted for its k-mer
+    assert np.array_equal(p["edit"][E][..., :7].sum(axis=3), np.repeat(top[:, :, None], k, axis=2))
+
+
+def test_small_dense_image_profiles():
+    """The einsum over bincount(idx) is the references' profile of the expanded windows; and an index fault shows:
+    any one boundary window reading a neighbour's text, or every window reading the text of the window a
+    (scaled-down) 2^32 bases below it, changes the expected flank sum and the expected edit sum."""
+    from tests.edit_cases import edit_profile_of
+    from tests.flank_cases import flank_profile_of
+
+    k, n_kmers, L, E = 16, 64, 100, 2
+    km, texts, per, markers, S, n_bases, marks, idx, held = small_dense(k, n_kmers, L)
+    p = lc.text_profiles(k, n_kmers, L, E)
+    n = lc.text_counts(idx, len(texts))
+    win = texts[idx]
+    hit, pos, _ = expected_positions(k, km, win, E)
+    start, _ = starts_of(k, km, win, hit, pos)
+    for plane in (0, E):
+        want = lc.image_profile(n, p["edit"][plane])
+        assert want.dtype == np.uint64 and np.array_equal(want, edit_profile_of(k, km, win, hit[plane], pos, start))
+        for D in lc.PROFILE_DEPTHS:
+            for with_start in (True, False):
+                want = lc.image_profile(n, p["flank"][D, plane, with_start])
+                assert np.array_equal(want, flank_profile_of(win, hit[plane], pos, start if with_start else None, D))
+    sums = lambda i: [lc.image_profile(lc.text_counts(i, len(texts)), a)  # noqa: E731
+                      for a in (p["flank"][8, E, True], p["flank"][32, E, True], p["flank"][8, 0, True], p["edit"][E])]
+    want = sums(idx)
+    for w in marks:
+        other = idx.copy()
+        other[w] = idx[w - 1] if w else idx[w + 1]
+        got = sums(other)  # (plane 0 aside: a marker text's pair may lie at distance 1 or 2)
+        assert not any(np.array_equal(a, b) for a, b in zip(got[:2] + got[3:], want[:2] + want[3:])), w
+    below = 64  # windows in the first scaled-down boundary, 64 S bases: what 2^32 / S is to the large image
+    shifted = idx.copy()
+    shifted[below:] = idx[:-below]
+    assert not any(np.array_equal(a, b) for a, b in zip(sums(shifted), want))
+    # a difference is reported with its cell
+    broken = want[0].copy()
+    broken[1, 5, 3, 2] += 1
+    msg = lc.first_cell(broken, want[0], ("side", "k-mer", "column", "symbol"))
+    assert msg.startswith("1 cells differ, first at {'side': 1, 'k-mer': 5, 'column': 3, 'symbol': 2}"), msg
+    assert lc.first_cell(want[0], want[0], ("side", "k-mer", "column", "symbol")) is None
 
 
 def decode(codes, nmask, start, length):
